@@ -7,8 +7,15 @@ binning -> k-means -> SNR -> scalars, plus the cohort histogram) over one batch 
 batch (weak scaling, no data-path collective); the cohort histogram is all-reduced over RCCL once
 per step when N > 1.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  Everything else
+the benchmark measures or checks -- the CPU baseline, the isolated runs of batch 0 (batch latency,
+per-kernel times, the roofline block), the per-study N4 times, the cohort all-reduce self-check and
+the host-to-host pipeline with its link probe -- runs only under --full; its fields are null in a
+plain run's line.
 """
 from __future__ import annotations
 
@@ -292,6 +299,42 @@ class stdout_to_stderr:
         os.close(self.saved)
 
 
+DUMP_SAMPLE = 1 << 21   # voxels per dumped map: 4 maps x 8 MiB as float32
+DUMP_SEED = 0
+RESULT_COLUMNS = ("vdp", "vdp_lb", "vdp_km", "defect_volume", "lung_volume", "snr", "mean_anchor",
+                  "p99", "n_mask", "n_defect", "n_lb12", "n_km0")
+
+
+def dump_outputs(dirpath, batch):
+    """--dump-outputs: what a caller of the timed path receives from ``batch`` (the batch of the
+    last timed step), one DIR/<name>.npy each: the N4-corrected volumes and the defect, border and
+    linear-binning maps as float32, the per-study scalars (RESULT_COLUMNS, then the 4 k-means
+    centres), N4 iteration counts and convergence values and the cohort histogram as float64.  Maps
+    of more than DUMP_SAMPLE voxels are written as a fixed sample: the flat C-order indices
+    sorted(default_rng(DUMP_SEED).integers(0, size, DUMP_SAMPLE)) of the [batch, R, C, Z] array,
+    the same for every map and every run of the same shape and batch."""
+    os.makedirs(dirpath, exist_ok=True)
+    n4, d, bo, lb, res = batch.download(n4=True)
+    idx = None
+    for name, a in (("n4hpvent", n4), ("defect", d), ("defect_border", bo), ("defect_lb", lb)):
+        if a is None:   # the dry run's stand-in computes no maps
+            continue
+        flat = a.reshape(-1)
+        if flat.size > DUMP_SAMPLE:
+            if idx is None:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_SAMPLE))
+            flat = flat[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), flat.astype(np.float32))
+    sc = np.array([[float(getattr(r, k, np.nan)) for k in RESULT_COLUMNS] +
+                   [float(v) for v in getattr(r, "km_centres", ())] for r in res], np.float64)
+    np.save(os.path.join(dirpath, "scalars.npy"), sc)
+    np.save(os.path.join(dirpath, "n4_iters.npy"),
+            np.array([list(r.n4_iters[:4]) for r in res], np.float64))
+    np.save(os.path.join(dirpath, "n4_conv.npy"),
+            np.array([list(getattr(r, "n4_conv", ())[:4]) for r in res], np.float64))
+    np.save(os.path.join(dirpath, "cohort_hist.npy"), batch.cohort_hist().astype(np.float64))
+
+
 def host_to_host(R, C, Z, nb, args, device, opts, seed, aligned=True, _lib=None):
     """Volumes/s from host memory to host memory: args.h2h_batches x nb studies streamed through
     vh_pipe in sub-batches of args.h2h_sub studies on args.h2h_slots slots (pinned staging, one
@@ -525,6 +568,14 @@ def make_parser():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="volumes per GPU")
     ap.add_argument("--shape", type=int, nargs=3, default=(128, 128, 24))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the "
+                         "isolated runs of batch 0 (batch latency, per-kernel times, roofline), the "
+                         "per-study N4 times, the cohort all-reduce self-check and the host-to-host "
+                         "pipeline with its link probe (the --no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float32 / float64; maps larger than a fixed size as a fixed seeded sample)")
     ap.add_argument("--no-n4", action="store_true", help="VDP chain only (N4 := identity)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -611,7 +662,7 @@ def main():
     nb = args.batch
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         cpu = cpu_baseline(R, C, Z, seconds=args.cpu_seconds, base_seed=shard_seed(0),
                            unique=BENCH_UNIQUE)   # before any GPU initialisation
 
@@ -653,7 +704,7 @@ def main():
                 sys.exit(f"bench.py: RCCL reports rank {r_rccl} of {n_rccl}, expected {rank} of {world}")
     vox = (1.5, 1.5, 10.0)
     opts = Bt.options(do_n4=not args.no_n4, vox=vox, do_cohort=True,
-                      profile=not args.no_profile, n4_subbatch=args.subbatch,
+                      profile=args.full and not args.no_profile, n4_subbatch=args.subbatch,
                       conv_threshold=args.conv_threshold, morph3d=args.morph3d,
                       n4_mode=args.n4_mode, conv_mode=args.conv_mode)
     warm = Bt.options(do_n4=not args.no_n4, vox=vox, do_cohort=True, profile=False,
@@ -703,7 +754,9 @@ def main():
     if dist:
         dt = max_over_ranks(dt, dist)
         rates = per_rank(nb * args.steps / t_local, dist)
-    if use_comm:
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, batches[(args.steps - 1) % ninf])
+    if use_comm and args.full:
         # after the timed region: one step of batch 0 without the collective, its local histogram,
         # then RCCL's sum of it checked against the per-rank histograms summed over gloo
         Bt.run(warm)
@@ -716,19 +769,20 @@ def main():
             comm["allreduce_ok"], comm["cohort_total"] = check_cohort(loc, red, dist)
         else:   # one rank: the sum over one rank is the local histogram
             comm["allreduce_ok"], comm["cohort_total"] = bool(np.array_equal(loc, red)), int(loc.sum())
-    _, _, _, _, res = Bt.download(n4=False, maps=False)
-    st_us = Bt.study_times()   # per-study wall time of the last step's one-workgroup-per-study N4
-    if os.environ.get("VH_STUDY_TRACE"):   # the other batches' placements too (A/B runs)
-        for b_ in batches[1:args.steps]:
-            b_.study_times()
-    tail = None
-    if st_us.max() > 0:
-        tail = {"min_us": round(float(st_us.min()), 1), "mean_us": round(float(st_us.mean()), 1),
-                "max_us": round(float(st_us.max()), 1),
-                "max_over_mean": round(float(st_us.max() / st_us.mean()), 4)}
+    res, tail = None, None
+    if args.full:
+        _, _, _, _, res = Bt.download(n4=False, maps=False)
+        st_us = Bt.study_times()   # per-study wall time of the last step's one-workgroup-per-study N4
+        if os.environ.get("VH_STUDY_TRACE"):   # the other batches' placements too (A/B runs)
+            for b_ in batches[1:args.steps]:
+                b_.study_times()
+        if st_us.max() > 0:
+            tail = {"min_us": round(float(st_us.min()), 1), "mean_us": round(float(st_us.mean()), 1),
+                    "max_us": round(float(st_us.max()), 1),
+                    "max_over_mean": round(float(st_us.max() / st_us.mean()), 4)}
     batch_latency_ms = None
     iso_kernels = {}   # class -> (summed ms, launches) over the isolated runs of batch 0
-    if ninf > 1 or not args.no_profile:
+    if args.full and (ninf > 1 or not args.no_profile):
         # batch 0 alone, args.iso_runs times (untimed above): the latency one batch sees, and every
         # kernel class's launch duration with no other batch's workgroups on the CUs -- what a
         # kernel-trace of one batch at a time reports (rocprofv3 --kernel-trace --stats of
@@ -796,14 +850,14 @@ def main():
         if chain:
             roof["non_n4_wall_us_per_step"] = round(
                 (kern.get("mask_stats", (0.0, 0))[0] + chain[0]) / runs * 1e3, 2)
-    its = np.array([list(r.n4_iters[:4]) for r in res])
+    its = np.array([list(r.n4_iters[:4]) for r in res]) if res is not None else None
     if not args.h2h_keep_batch:
         # the device-resident batches (their streams, 1.5 GB of HBM each) are done: the pipe's slot
         # streams then have the GPU_MAX_HW_QUEUES (4) hardware queues to themselves
         for b_ in batches:
             b_.close()
     h2h = None
-    if not args.no_h2h:
+    if args.full and not args.no_h2h:
         if dist:   # every rank streams at once (host memory and PCIe shared as in a cohort run)
             dist.barrier()
         h2h = host_to_host(R, C, Z, nb, args, local, warm, shard_seed(rank) + 500, _lib=_lib)
@@ -836,11 +890,13 @@ def main():
                    "distinct_studies_per_gpu": min(nb, BENCH_UNIQUE) * ninf, "lung_geometry": "per study",
                    "parallelism": f"dp{world}", "n4_subbatch": args.subbatch or nb,
                    "batches_in_flight": ninf,
-                   "n4_iterations_mean": float(its.sum(axis=1).mean()) if its.size else 0.0},
+                   "n4_iterations_mean": None if its is None else
+                                         float(its.sum(axis=1).mean()) if its.size else 0.0},
         "roofline": roof,
         "cpu_baseline": cpu,
         "n4_study_times": tail,
-        "batch_latency_ms": batch_latency_ms if ninf > 1 else round(dt / args.steps * 1e3, 3),
+        "batch_latency_ms": (batch_latency_ms if ninf > 1 else round(dt / args.steps * 1e3, 3))
+                            if args.full else None,
         "host_to_host_vol_s": round(world * h2h["volumes"] / h2h["seconds"], 2) if h2h else None,
         "host_to_host": h2h,
     }
@@ -850,7 +906,7 @@ def main():
         line["per_rank_vol_s"] = [round(r, 2) for r in rates]
     if rank == 0:
         print(json.dumps(line), flush=True)
-    if comm and not comm["allreduce_ok"]:
+    if comm and not comm.get("allreduce_ok", True):
         sys.exit("bench.py: the RCCL cohort all-reduce differs from the sum of the per-rank histograms")
     if args.h2h_keep_batch:
         for b_ in batches:

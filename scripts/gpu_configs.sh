@@ -10,7 +10,8 @@
 # (scripts/gpu_pmc1.sh); NOPMC=1 skips them here.
 # usage: [NOPMC=1] [CONFIGS="config2 config5"] [TRACE=config5] scripts/gpu_configs.sh TAG
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-out}   # results directory
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${1:-r6}
 declare -A WL STEPS
@@ -24,17 +25,17 @@ for c in ${CONFIGS-config2 config5}; do
   if [ -z "$NOPMC" ]; then
   REGEX='k_n4_|k_plane|k_sort|k_kmeans' BENCH_ARGS="${WL[$c]}" bash scripts/gpu_pmc.sh ${TAG}_${c}_pmc
   rc=$?; echo "$c pmc rc=$rc"; [ $rc -eq 0 ] || exit $rc
-  cp gpurun_out/${TAG}_${c}_pmc_traffic.json profiles/${TAG}_${c}_pmc_traffic.json
+  cp $OUT/${TAG}_${c}_pmc_traffic.json profiles/${TAG}_${c}_pmc_traffic.json
   fi
-  timeout -k 10 600 python3 bench.py ${WL[$c]} ${STEPS[$c]} --no-cpu-baseline --no-h2h > gpurun_out/${TAG}_${c}.json 2> gpurun_out/${TAG}_${c}.err
-  rc=$?; echo "$c bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/${TAG}_${c}.err; exit $rc; }
+  timeout -k 10 600 python3 bench.py --full ${WL[$c]} ${STEPS[$c]} --no-cpu-baseline --no-h2h > $OUT/${TAG}_${c}.json 2> $OUT/${TAG}_${c}.err
+  rc=$?; echo "$c bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/${TAG}_${c}.err; exit $rc; }
 done
 if [ -n "${TRACE-config5}" ]; then
   c=${TRACE-config5}
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_${c}_prof -o run -- \
-      python3 bench.py ${WL[$c]} ${STEPS[$c]} --inflight 1 --no-cpu-baseline --no-h2h --no-profile > gpurun_out/${TAG}_${c}_prof.log 2>&1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${c}_prof -o run -- \
+      python3 bench.py --full ${WL[$c]} ${STEPS[$c]} --inflight 1 --no-cpu-baseline --no-h2h --no-profile > $OUT/${TAG}_${c}_prof.log 2>&1
   rc=$?; echo "$c rocprof rc=$rc"
-  if [ $rc -eq 139 ] && ls gpurun_out/${TAG}_${c}_prof/*kernel_stats.csv > /dev/null 2>&1; then
+  if [ $rc -eq 139 ] && ls $OUT/${TAG}_${c}_prof/*kernel_stats.csv > /dev/null 2>&1; then
     echo "$c: rocprofv3's exit-time segfault after the stats were written (cooperative launch)"; exit 0
   fi
   exit $rc

@@ -8,7 +8,8 @@
 # CSV present counts as that line done, and nothing more runs on the GPU after it.
 # usage: [LINES="config2 ci"] [PROF="ci comm1"] scripts/gpu_lines.sh TAG
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-out}   # results directory
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${1:-r2}
 declare -A ARGS
@@ -19,14 +20,14 @@ ARGS[comm1]="--comm --steps 5 --warmup 1 --no-cpu-baseline --no-h2h"
 LINES=${LINES-config2 config5 ci comm1}
 PROF=${PROF-ci comm1 config2}
 for name in $LINES; do
-  timeout -k 10 600 python3 bench.py ${ARGS[$name]} > gpurun_out/${TAG}_${name}.json 2> gpurun_out/${TAG}_${name}.err
-  rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/${TAG}_${name}.err; exit $rc; }
+  timeout -k 10 600 python3 bench.py --full ${ARGS[$name]} > $OUT/${TAG}_${name}.json 2> $OUT/${TAG}_${name}.err
+  rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/${TAG}_${name}.err; exit $rc; }
 done
 for name in $PROF; do
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_${name}_prof -o run -- \
-      python3 bench.py ${ARGS[$name]} --no-profile > gpurun_out/${TAG}_${name}_prof.log 2>&1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${name}_prof -o run -- \
+      python3 bench.py --full ${ARGS[$name]} --no-profile > $OUT/${TAG}_${name}_prof.log 2>&1
   rc=$?; echo "$name rocprof rc=$rc"
-  if [ $rc -eq 139 ] && ls gpurun_out/${TAG}_${name}_prof/*kernel_stats.csv > /dev/null 2>&1; then
+  if [ $rc -eq 139 ] && ls $OUT/${TAG}_${name}_prof/*kernel_stats.csv > /dev/null 2>&1; then
     echo "$name: rocprofv3's exit-time segfault after the stats were written; stopping here"; exit 0
   fi
   [ $rc -eq 0 ] || exit $rc

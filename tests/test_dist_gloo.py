@@ -81,7 +81,7 @@ def _bench(cmd, env=None, timeout=300):
                           text=True, timeout=timeout)
 
 
-DRY = ["--dry-run", "--steps", "2", "--warmup", "1", "--batch", str(PER_RANK), "--shape",
+DRY = ["--dry-run", "--full", "--steps", "2", "--warmup", "1", "--batch", str(PER_RANK), "--shape",
        *map(str, SHAPE), "--inflight", "2", "--iso-runs", "2", "--h2h-batches", "2", "--h2h-sub", "2",
        "--h2h-slots", "2"]
 
@@ -133,6 +133,58 @@ def test_bench_gpus_n_launches_n_ranks(world):
     r = _bench(["bench.py", "--gpus", str(world)] + DRY)
     assert r.returncode == 0, r.stderr[-2000:]
     _check_dry_line(r.stdout, world)
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only (the extras' fields are null and
+    the cohort self-check is not run); --dump-outputs writes the last timed step's outputs as
+    float32 / float64 .npy files, the same from run to run."""
+    import json
+    plain = [a for a in DRY if a != "--full"]
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench(["bench.py", "--gpus", "2"] + plain + ["--dump-outputs", str(tmp_path / d)],
+                   env={"VH_DRY_BAD_SUM": "1"})   # only --full's self-check would notice
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout)
+        assert line["steps"] == 2 and line["n_gpus"] == 2 and line["value"] > 0
+        assert line["ms_per_step"] > 0 and line["unit"] == "volumes/s" and line["dtype"] == "f32"
+        for k in ("roofline", "cpu_baseline", "n4_study_times", "batch_latency_ms", "host_to_host",
+                  "host_to_host_vol_s"):
+            assert line[k] is None, k
+        assert "allreduce_ok" not in line["comm"]
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert set(dumps[0]) == {"scalars.npy", "n4_iters.npy", "n4_conv.npy", "cohort_hist.npy"}
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][f], equal_nan=True)
+    # the last timed step (step 1 of 2) ran batch 1 of the 2 in flight: rank 0's second 3 studies
+    x, m = synth_batch(*SHAPE, PER_RANK, base_seed=bench.shard_seed(0) + bench.BENCH_UNIQUE, vary=True)
+    assert dumps[0]["cohort_hist.npy"].sum() >= cohort_hist(x, m).sum() > 0
+    assert dumps[0]["n4_iters.npy"].shape == (PER_RANK, 4)
+
+
+def test_dump_outputs_samples_large_maps(tmp_path):
+    """dump_outputs on a batch with maps: small maps whole, large ones as the fixed seeded sample."""
+    class B:
+        def __init__(self, n):
+            self.n4 = np.arange(n, dtype=np.float32).reshape(1, n, 1, 1)
+
+        def download(self, n4=False):
+            u = (self.n4 % 2).astype(np.uint8)
+            return self.n4, u, u, u, []
+
+        def cohort_hist(self):
+            return np.zeros(BINS, np.uint64)
+
+    bench.dump_outputs(str(tmp_path / "s"), B(100))
+    assert np.array_equal(np.load(tmp_path / "s" / "n4hpvent.npy"), np.arange(100, dtype=np.float32))
+    n = bench.DUMP_SAMPLE + 1000
+    bench.dump_outputs(str(tmp_path / "l"), B(n))
+    got = np.load(tmp_path / "l" / "n4hpvent.npy")
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_SAMPLE))
+    assert got.dtype == np.float32 and np.array_equal(got, idx.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "l" / "defect_lb.npy"), (idx % 2).astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "l" / f) for f in os.listdir(tmp_path / "l")) < 64 << 20
 
 
 def test_bench_under_torchrun():

@@ -22,9 +22,6 @@ def test_table_matches_reference_checksum(name):
     assert t.shape == (p["rows"], 4) and t.dtype == np.float64
     assert hashlib.sha256(np.ascontiguousarray(t).tobytes()).hexdigest() == p["sha256"]
     assert len(radii_indices(t)) == p["bounds"]
-    ref = os.path.join("/root/reference", name)
-    if os.path.exists(ref):   # authoring container only; the GPU box has no reference
-        assert np.array_equal(np.load(ref, allow_pickle=False), t)
 
 
 def test_radii_indices_matches_reference_formula():
