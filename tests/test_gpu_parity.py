@@ -1,6 +1,7 @@
 """GPU parity tests (MI355X): the HIP path through the C-ABI against the reference goldens and the
 CPU oracle.  Tolerances: masks / indices / counts bit-exact; VDP scalars exact (they are ratios of
 exact counts); SNR rel 1e-5; N4 rel 1e-5 (north_star), identical iteration counts."""
+import functools
 import hashlib
 import os
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_case, golden_files
+from test_bin_min_lemma import r3_bin_min
 from oracle import native, vdp_oracle as O
 from vent_analysis_amd import _lib
 from vent_analysis_amd.sphere import compact_table, sphere_pix
@@ -1116,6 +1118,43 @@ def test_n4_grid_any_workgroup_count(G, monkeypatch):
         assert np.array_equal(o[0], base[0]) and np.array_equal(o[1], base[1])
         assert list(o[4][0].n4_iters[:4]) == list(base[4][0].n4_iters[:4])
         assert o[4][0].n4_conv[:4] == base[4][0].n4_conv[:4]
+
+
+@functools.lru_cache(maxsize=None)
+def _rising_run_case():
+    """A 24x20x6 study with a box mask whose first 20 masked voxels (raster order: C order of
+    [R][C][Z], find_first's order) strictly increase; its oracle and sweep-driver results."""
+    X, M = synth_volume(24, 20, 6, 31)
+    M = np.zeros_like(M)
+    M[4:20, 3:17, 1:5] = 1
+    first = np.argwhere(M > 0)[:20]
+    base = float(X[M > 0].mean())
+    X[tuple(first.T)] = (base * (1.0 + 0.03 * np.arange(20))).astype(np.float32)
+    ref = native.n4(X, M)
+    sweep = _run_one(X, M, "sweep")
+    return X, M, ref, sweep
+
+
+@pytest.mark.parametrize("driver,G", [("study", None), ("grid", None), ("grid", "3")])
+def test_n4_exact_bin_minimum_path(driver, G, monkeypatch):
+    """The raster-scan bin minimum (exact_min_study, the M.exact branch): the initial strictly
+    increasing run of U outlasts the first 16 masked voxels, so r3_bin_min cannot decide and the
+    whole workgroup scans the study.  With VH_STG_G=3 every workgroup of the grid form runs the scan
+    redundantly while the sums cross workgroups."""
+    X, M, (ref, its_ref, conv_ref), s = _rising_run_case()
+    # L0 = U of level 0's first iteration: the mirror of the device function must give up on it
+    L0 = np.log(X[M > 0].astype(np.float64)).astype(np.float32)
+    assert np.all(np.diff(L0[:20]) > 0)
+    assert r3_bin_min(L0) is None
+    monkeypatch.delenv("VH_STG_G", raising=False)
+    if G is not None:
+        monkeypatch.setenv("VH_STG_G", G)
+    o = _run_one(X, M, driver)   # (an "LDS budget" error fails the test)
+    assert_n4_matches(o[0][0], o[4][0].n4_iters[:4], o[4][0].n4_conv[:4], ref, its_ref, conv_ref, 0,
+                      ("exact bin minimum", driver, G))
+    assert np.array_equal(o[0], s[0])
+    assert list(o[4][0].n4_iters[:4]) == list(s[4][0].n4_iters[:4])
+    assert o[4][0].n4_conv[:4] == s[4][0].n4_conv[:4]
 
 
 def test_n4_grid_empty_and_tiny_masks():

@@ -1,6 +1,5 @@
 // n4_study.hip -- volume-resident N4 bias-field correction on gfx950: ONE workgroup (1024 threads,
-// 16 waves; ST_TPB=512 builds: 8 waves, two studies per CU) per study runs the whole multi-level
-// iteration loop of
+// 16 waves) per study runs the whole multi-level iteration loop of
 // sitk.N4BiasFieldCorrectionImageFilter (Vent_Analysis.py:316-334; build spec
 // S1-S9 in oracle/n4_oracle.c, which this kernel matches bit for bit) in a single launch.  Between
 // sweeps the study's small state -- B-spline lattice, level tables, histogram, FFT buffers, E(u)
@@ -28,23 +27,16 @@
 // Work items are taken from an LDS counter; every reduction is either integer (order-free) or in
 // a fixed order, so results are deterministic.
 //
-// Round 4: 153 -> 70 KB of LDS per study (P1 pair, denominators and the second table set out of
-// LDS, 4 histogram copies in the emap's DEN buffer) at unchanged speed, so that ST_TPB=512 builds
-// fit two studies per CU.  Measured: two 512-thread studies on a CU
-// take 1.37x as long as one alone, 1.46x the CU's throughput -- but one alone takes 1.26x as long
-// as a 1024-thread study (128 VGPRs and half the waves for the latency-bound fit and eval walks),
-// and 256-study batches do not keep both slots fed (the next batch's short kernels wait for CUs
-// that two studies fill), so 1024 threads stay the default.  The serial-chain variant of S7 (chain
-// waves beside the compute waves, 46-54 ms per bench step against PC's 33 ms) is gone.
+// The phases are functions (study_item_order ... study_empty_exit below) shared with the grid
+// form k_n4_studyg, which runs ONE study over several cooperating workgroups; each kernel is the
+// level / iteration skeleton around them plus what is its own.
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
 
 #include "n4_shared.h"
 
-#ifndef ST_TPB
-#define ST_TPB 1024
-#endif
+#define ST_TPB 1024   // threads of a workgroup: pcw_run's one block per thread is built on it
 #define ST_WAVES (ST_TPB / 64)
 #define ST_HC 4        // LDS histogram copies (in the emap's DEN buffer, free until the Wiener pass)
 #define ST_NFIRST 16   // first masked voxels (raster order) tracked for the bin minimum (n4_shared.h r3_bin_min)
@@ -55,8 +47,6 @@
 #ifndef ST_EVAL_EXP
 #define ST_EVAL_EXP 0   // 1: eval stores p = expf_cr(d) for PC (its pass 0 then skips the exp)
 #endif
-// 1024 only: the round-4 512-thread build (two studies per CU) no longer
-// converges since the round-5/6 PC changes (r6t: every level runs 50 iterations) and is not kept up
 static_assert(ST_TPB == 1024, "pcw_run takes the whole workgroup (one block per thread)");
 constexpr int ST_NB = 2;   // U buffers: the last computed field's and the one being computed
 
@@ -117,7 +107,6 @@ struct StudyMisc {
     float bin_min, slope, bmax, pad;
 #ifdef ST_PROF
     unsigned long long fprof[4];   // wave of thread st_pt: fit rows / push / contract / items
-    unsigned long long sprof[4];   // emap series of thread 300 (h in range): total, hist sums, kernel exp, twiddle
 #endif
     double sd, sd2, conv;
     ChainState ch;             // PC's result (conv of the last iteration)
@@ -439,13 +428,6 @@ __device__ void eval_item(const Item &it, int item, int Z, int CZ, const TabV &T
 // strided passes below hit distinct LDS banks.  Only wave-local ordering is needed.
 // ---------------------------------------------------------------------------------------------
 #define ST_FFT_N (VH_FFT_P + VH_FFT_P / 8)   // padded slots of one transform
-#ifndef ST_WPAR
-// E-map: the pointwise steps between the FFTs run on all threads, as passes of their own (3: the
-// Wiener filter, the clamp / moment series and the kernel product; 2: not the product; 1: only the
-// filter; 0: all inside the one- or two-wave FFTs' first / last passes, round 4).  Bit-identical
-// arithmetic; 3 is 5 % faster on the study kernel (DESIGN_LOG.md round 5).
-#define ST_WPAR 3
-#endif
 __device__ __forceinline__ int fpad(int i) { return i + (i >> 3); }
 
 struct FftId {
@@ -517,33 +499,27 @@ __device__ void exact_row(const StudyArgs &a, int64_t b, const float *Ub, int x,
     }
 }
 
-// The workgroup's barrier (the phases below were once shared with a subset of the waves)
-struct Grp {
-    int t, n, w, nw;   // thread / threads, wave / waves of the group
-};
-__device__ __forceinline__ void gsync(const Grp &, StudyMisc &) { __syncthreads(); }
-
+// The whole workgroup; s_cmax and s_min hold ST_TPB floats each.  The result is thread 0's.
 __device__ float exact_min_study(const StudyArgs &a, int64_t b, const float *Ub, float *s_cmax,
-                                 float *s_min, const Grp &g, StudyMisc &M) {
-    const int t = g.t;
-    const int per = (a.R + g.n - 1) / g.n;
+                                 float *s_min, int t) {
+    const int per = (a.R + ST_TPB - 1) / ST_TPB;
     const int s0 = min(t * per, a.R), e0 = min(s0 + per, a.R);
     float cmax = -FLT_MAX, dummy = FLT_MAX;
     for (int x = s0; x < e0; ++x) exact_row(a, b, Ub, x, cmax, dummy, false);
     s_cmax[t] = cmax;
-    gsync(g, M);
+    __syncthreads();
     if (t == 0) {
         float run = -FLT_MAX;
-        for (int i = 0; i < g.n; ++i) { const float v = s_cmax[i]; s_cmax[i] = run; run = v > run ? v : run; }
+        for (int i = 0; i < ST_TPB; ++i) { const float v = s_cmax[i]; s_cmax[i] = run; run = v > run ? v : run; }
     }
-    gsync(g, M);
+    __syncthreads();
     float run = s_cmax[t], mn = FLT_MAX;
     for (int x = s0; x < e0; ++x) exact_row(a, b, Ub, x, run, mn, true);
     s_min[t] = mn;
-    gsync(g, M);
+    __syncthreads();
     float m = FLT_MAX;
     if (t == 0)
-        for (int i = 0; i < g.n; ++i) m = s_min[i] < m ? s_min[i] : m;
+        for (int i = 0; i < ST_TPB; ++i) m = s_min[i] < m ? s_min[i] : m;
     return m;
 }
 
@@ -580,10 +556,405 @@ __device__ __forceinline__ int next_item(StudyMisc &M, const int32_t *ordr, int 
     return item >= nitems ? -1 : uni(ordr[item]);
 }
 
+// =============================================================================================
+// The phases of the level / iteration loop, shared by k_n4_study and k_n4_studyg.  Each runs on the
+// whole workgroup.  Where the kernels differ only in where a value comes from, the caller passes
+// it as a functor; next() hands the calling wave its next item of the pass (-1: none left).
+// =============================================================================================
+
+// Item schedule: items by row count, largest first (ties by index), so the dynamic item queue of
+// every pass ends on small items; the item order of every reduction is unchanged.  isz: nitems
+// ints of scratch.
+__device__ __forceinline__ void study_item_order(const StudyArgs &a, int64_t b, int32_t *isz, int32_t *ordr) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    for (int item = wv; item < a.nitems; item += ST_WAVES) {
+        Item it;
+        const bool any = study_item(it, a, b, item);
+        if (lane == 0) isz[item] = any ? it.xe - it.xs + 1 : 0;
+    }
+    __syncthreads();
+    for (int i = t; i < a.nitems; i += ST_TPB) {
+        const int si = isz[i];
+        int rank = 0;
+        for (int j = 0; j < a.nitems; ++j) {
+            const int sj = isz[j];
+            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
+        }
+        ordr[rank] = i;
+    }
+    __syncthreads();
+}
+
+// L0, U = L0 (U buffer 0) and its range over the items of next()
+template <class Next>
+__device__ __forceinline__ void init_pass(const StudyArgs &a, int64_t b, const Next &next, float *Lb, int64_t n,
+                                          float4 *rpart) {
+    for (;;) {
+        const int item = next();
+        if (item < 0) break;
+        Item it;
+        if (!study_item(it, a, b, item)) {
+            if ((threadIdx.x & 63) == 0) rpart[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
+            continue;
+        }
+        init_item(a, b, it, item, Lb, a.U + b * a.VS, n, rpart);
+    }
+}
+
+// One level's tables and weights as staged in LDS by level_begin
+struct LevelW {
+    TabV T;
+    int ncx, ncy, ncz, nlat;
+    double *Wk3, *Wk2;    // dense slice weights [ncz][Z] (w^3, w^2)
+    double2 *Wx3, *Wx2;   // row weights [R][4] doubles (w^3 / sum w^2, w^2; wave-uniform reads)
+};
+
+// Stages the level's tables and weights (no barrier: the caller's next one publishes them)
+__device__ __forceinline__ LevelW level_begin(const StudyArgs &a, const DevLevel &lv, char *smem) {
+    const int t = threadIdx.x;
+    LevelW W;
+    char *tabp = smem + a.o_tab;
+    load_tables(tab_w(tabp, a.R, a.C, a.Z, a.kcap), lv, a.R, a.C, a.Z);
+    W.T = tab_view(tabp, a.R, a.C, a.Z, a.kcap);
+    W.ncx = lv.ax[0].ncp;
+    W.ncy = lv.ax[1].ncp;
+    W.ncz = lv.ax[2].ncp;
+    W.nlat = W.ncx * W.ncy * W.ncz;
+    W.Wk3 = reinterpret_cast<double *>(smem + a.o_wk);
+    W.Wk2 = W.Wk3 + (size_t)W.ncz * a.Z;
+    for (int e = t; e < W.ncz * a.Z; e += ST_TPB) {
+        W.Wk3[e] = lv.wk3[e];
+        W.Wk2[e] = lv.wk2[e];
+    }
+    W.Wx3 = reinterpret_cast<double2 *>(smem + a.o_wx);
+    W.Wx2 = W.Wx3 + 2 * a.R;
+    for (int x = t; x < a.R; x += ST_TPB) {
+        const double2 *w3 = reinterpret_cast<const double2 *>(lv.ax[0].w3i + 4 * x);
+        const double2 *w2 = reinterpret_cast<const double2 *>(lv.ax[0].w2 + 4 * x);
+        W.Wx3[2 * x] = w3[0];
+        W.Wx3[2 * x + 1] = w3[1];
+        W.Wx2[2 * x] = w2[0];
+        W.Wx2[2 * x + 1] = w2[1];
+    }
+    return W;
+}
+
+// The fit (MODE 0: numerators) or denominator (MODE 1) pass over the items of next(), into the
+// zeroed 128-bit fixed-point LDS lattice numfix
+template <int MODE, class Next>
+__device__ __forceinline__ void fit_pass(const StudyArgs &a, int64_t b, StudyMisc &M, const Next &next,
+                                         const LevelW &W, const float *Ub, int64_t n, const float *sE, float bmin,
+                                         double rinv, FitRing &ring, unsigned long long *numfix,
+                                         unsigned long long *fprof = nullptr) {
+    for (int e = threadIdx.x; e < 2 * W.nlat; e += ST_TPB) numfix[e] = 0ull;
+    if (threadIdx.x == 0) M.item_ctr = 0;
+    __syncthreads();
+    for (;;) {
+        const int item = next();
+        if (item < 0) break;
+        Item it;
+        if (!study_item(it, a, b, item)) continue;
+        fit_item<MODE, true>(it, W.T, MODE ? W.Wk2 : W.Wk3, MODE ? W.Wx2 : W.Wx3, W.ncy, W.ncz, a.Z, a.bins, Ub,
+                             n, sE, bmin, rinv, ring, a.nb_ring, numfix, fprof);
+    }
+    __syncthreads();
+}
+
+// one wave: the items' exact-CoV sums added in item order (S7x), on lane 0
+__device__ __forceinline__ void s7x_sums(const double *ipart, int nitems, double &sd, double &sd2) {
+    sd = sd2 = 0.0;
+    for (int i = threadIdx.x & 63; i < nitems; i += 64) {
+        sd += ipart[2 * i];
+        sd2 += ipart[2 * i + 1];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        sd += __shfl_down(sd, off, 64);
+        sd2 += __shfl_down(sd2, off, 64);
+    }
+}
+
+// one wave: the Range3 records rec[0 .. count) merged (order-free)
+__device__ __forceinline__ Range3 r3_of(float4 p) {
+    Range3 o;
+    o.mx = p.x; o.m1 = p.y; o.m2 = p.z; o.m3 = p.w;
+    return o;
+}
+__device__ __forceinline__ Range3 r3_merge_records(const float4 *rec, int count) {
+    Range3 r;
+    r3_init(r);
+    for (int i = threadIdx.x & 63; i < count; i += 64) r3_merge(r, r3_of(rec[i]));
+    return r3_wave(r);
+}
+
+// ctrl (one wave): ITK's while-condition on the previous iteration's convergence value (conv(),
+// called by lane 0 when itn > 0), then the bin range of the field in Ub from its merged range r.
+// Leaves M.stop, or M.bin_min / M.slope, or M.exact (the raster scan decides: exact_bin_min).
+template <class Conv>
+__device__ __forceinline__ void ctrl_decide(const StudyArgs &a, StudyMisc &M, const Range3 &r, const float *Ub,
+                                            int itn, int L, const Conv &conv) {
+    const int lane = threadIdx.x & 63;
+    if (lane < M.nfirst) M.fu[lane] = Ub[M.foff[lane]];   // the run's values
+    wave_lds_order();
+    if (lane == 0) {
+        M.stop = 0;
+        M.exact = 0;
+        if (itn > 0) {
+            M.conv = conv();
+            if (!(M.conv > (double)a.thresh) || itn >= a.lvs->max_iters[L]) M.stop = 1;
+        }
+        if (!M.stop) {
+            float bmin;
+            M.bmax = r.mx;
+            if (r3_bin_min(r, M.fu, M.nfirst, bmin)) {
+                M.bin_min = bmin;
+                M.slope = (r.mx - bmin) / (float)(a.bins - 1);
+            } else {
+                M.exact = 1;
+            }
+        }
+    }
+}
+
+// M.exact (rare): the bin minimum by the raster scan of the study (exact_min_study)
+__device__ __forceinline__ void exact_bin_min(const StudyArgs &a, int64_t b, const float *Ub, char *scr,
+                                              StudyMisc &M) {
+    float *s_cmax = reinterpret_cast<float *>(scr);
+    const float m = exact_min_study(a, b, Ub, s_cmax, s_cmax + ST_TPB, threadIdx.x);
+    if (threadIdx.x == 0) {
+        M.bin_min = m;
+        M.slope = (M.bmax - m) / (float)(a.bins - 1);
+    }
+    __syncthreads();
+}
+
+// emap scratch: V (= U = NUM), F, DEN, twiddles; the ST_HC histogram copies sit in DEN (read by the
+// series loop, which writes V and F; DEN is written after it)
+struct EmapW {
+    double2 *V, *F, *DEN, *TW;
+    unsigned long long *Hc;
+};
+__device__ __forceinline__ EmapW emap_w(char *scr) {
+    static_assert(sizeof(unsigned long long) * ST_HC * VH_MAX_BINS <= sizeof(double2) * ST_FFT_N,
+                  "histogram copies fit the DEN buffer");
+    EmapW w;
+    w.V = reinterpret_cast<double2 *>(scr);
+    w.F = w.V + ST_FFT_N;
+    w.DEN = w.F + ST_FFT_N;
+    w.TW = w.DEN + ST_FFT_N;
+    w.Hc = reinterpret_cast<unsigned long long *>(w.DEN);
+    return w;
+}
+
+// hist (S3): compact U[j_begin, j_end) (j_begin a multiple of 16) into the packed LDS histogram
+// copies, 16 values per thread and trip, one 64-bit add per value
+__device__ __forceinline__ void hist_slice(const float *Ub, int64_t j_begin, int64_t j_end,
+                                           unsigned long long *Hc, float bmin, double rinv, int bins) {
+    const int t = threadIdx.x;
+    for (int i = t; i < ST_HC * VH_MAX_BINS; i += ST_TPB) Hc[i] = 0ull;
+    __syncthreads();
+    unsigned long long *H = Hc + (t & (ST_HC - 1)) * VH_MAX_BINS;
+    for (int64_t j0 = j_begin + (int64_t)t * 16; j0 < j_end; j0 += (int64_t)ST_TPB * 16) {
+        float u[16];
+        if (j0 + 16 <= j_end) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 v = reinterpret_cast<const float4 *>(Ub + j0)[q];
+                u[4 * q] = v.x; u[4 * q + 1] = v.y; u[4 * q + 2] = v.z; u[4 * q + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) u[k] = j0 + k < j_end ? Ub[j0 + k] : __int_as_float(0x7fc00000);
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            int idx;
+            const unsigned long long w = hist_pack(u[k], bmin, rinv, bins, idx);
+            atomicAdd(&H[idx], w);
+        }
+    }
+    __syncthreads();
+}
+
+// emap (S4; same arithmetic as n4.hip k_n4_emap and the oracle): E(u) of the bins into sE.
+// series(h): the 64-bit S3 sum of bin h (24 fraction bits).  Only the five FFT calls run on one or
+// two waves; the pointwise passes between them (Wiener filter, clamp / moment series, kernel
+// product) run on all threads as passes of their own, each with its barrier: inside the FFTs'
+// first / last passes the divisions ran 8 deep on one wave (5 % of the study kernel, DESIGN_LOG.md
+// round 5).
+template <class Series>
+__device__ __forceinline__ void emap_phase(const StudyArgs &a, const EmapW &w, float *sE, float bmin, float slope,
+                                           const Series &series) {
+    const int t = threadIdx.x, wv = t >> 6;
+    double2 *const V = w.V, *const F = w.F, *const DEN = w.DEN, *const TW = w.TW;
+    const int P = VH_FFT_P, bins = a.bins, off = (P - bins) / 2;
+    const float sFWHM = a.fwhm / slope;
+    const float ef = (float)(4.0 * LN2 / (double)(sFWHM * sFWHM));
+    const float sf = (float)(2.0 * sqrt(LN2 / PI_D) / (double)sFWHM);
+    static_assert(VH_FFT_P / 2 <= ST_TPB, "one twiddle per thread");
+    const double2 twv = t < P / 2 ? a.tw[t] : make_double2(0.0, 0.0);   // in flight
+    for (int i = t; i < P; i += ST_TPB) {   // histogram series and Gaussian kernel
+        const int h = i - off;
+        const unsigned long long s = h >= 0 && h < bins ? series(h) : 0ull;
+        V[fpad(i)] = make_double2((double)s * (1.0 / 16777216.0), 0.0);
+        double fx;
+        if (i == 0) {
+            fx = (double)sf;
+        } else if (i == P / 2) {
+            fx = (double)sf * exp(-0.25 * (double)((float)P * (float)P) * (double)ef);
+        } else {
+            const float nf = (float)(i < P / 2 ? i : P - i);
+            fx = (double)(sf * expf_cr_tail(-(nf * nf) * ef));
+        }
+        F[fpad(i)] = make_double2(fx, 0.0);
+    }
+    if (t < P / 2) TW[t] = twv;
+    __syncthreads();
+    if (wv < 2) wave_fft_lds(wv ? F : V, TW, false, FftId(), FftId());
+    __syncthreads();
+    for (int i = t; i < P; i += ST_TPB) {   // Wiener filter
+        const double2 f = F[fpad(i)], v = V[fpad(i)];
+        const double fa = f.x, fb = f.y;
+        const double gg = fa / ((fa * fa - (-fb) * fb) + (double)a.noise);
+        V[fpad(i)] = make_double2(v.x * gg, v.y * gg);
+    }
+    __syncthreads();
+    if (wv == 0) wave_fft_lds(V, TW, true, FftId(), FftId());   // inverse
+    __syncthreads();
+    for (int i = t; i < P; i += ST_TPB) {   // clamp; the moment series' points
+        const double2 v = V[fpad(i)];
+        const double ur = v.x > 0.0 ? v.x : 0.0;
+        const float c = bmin + ((float)i - (float)off) * slope;
+        DEN[fpad(i)] = make_double2(ur, 0.0);
+        V[fpad(i)] = make_double2((double)c * ur, 0.0);
+    }
+    __syncthreads();
+    // each series: forward, times the kernel's transform, inverse
+    if (wv < 2) wave_fft_lds(wv ? DEN : V, TW, false, FftId(), FftId());
+    __syncthreads();
+    for (int e = t; e < 2 * P; e += ST_TPB) {
+        double2 *const x = e < P ? V : DEN;
+        const int i = e < P ? e : e - P;
+        const double2 f = F[fpad(i)], v = x[fpad(i)];
+        const double fa = f.x, fb = f.y;
+        x[fpad(i)] = make_double2(v.x * fa - v.y * fb, v.x * fb + v.y * fa);
+    }
+    __syncthreads();
+    if (wv < 2) wave_fft_lds(wv ? DEN : V, TW, true, FftId(), FftId());
+    __syncthreads();
+    for (int i = t; i < bins; i += ST_TPB) {
+        const double d = DEN[fpad(i + off)].x;
+        sE[i] = d != 0.0 ? (float)(V[fpad(i + off)].x / d) : 0.0f;
+    }
+    __syncthreads();
+}
+
+// lat (S6): lattice += phi = num / den of every control point (no barrier)
+template <class DenOf, class NumOf>
+__device__ __forceinline__ void lattice_update(float *lat, int nlat, const DenOf &den_of, const NumOf &num_of) {
+    for (int e = threadIdx.x; e < nlat; e += ST_TPB) {
+        const double d = den_of(e);
+        const double num = num_of(e);
+        const float phi = d != 0.0 ? (float)(num / d) : 0.0f;
+        lat[e] += phi;
+    }
+}
+
+// P1[ij][z]: the lattice [nij][ncz] contracted over slices with the staged level's z tables
+__device__ __forceinline__ void p1_from_lattice(const float *lat, const TabV &T, int nij, int ncz, int Z,
+                                                double *out) {
+    for (int e = threadIdx.x; e < nij * Z; e += ST_TPB) {
+        const int ij = e / Z, z = e % Z;
+        const float4 w = T.wz[z];
+        const float *l = lat + ij * ncz + T.bz[z];
+        out[e] = (double)w.x * (double)l[0] + (double)w.y * (double)l[1] +
+                 (double)w.z * (double)l[2] + (double)w.w * (double)l[3];
+    }
+}
+
+// eval over the items of next(): iteration itk of level L; U into Uo, d into D, this field's T
+// windows into Tg buffer tpar ^ 1 (the old field's are in tpar), the items' ranges into rp_out and
+// (conv_mode 1) their exact-CoV sums into ipart
+template <class Next>
+__device__ __forceinline__ void eval_pass(const StudyArgs &a, int64_t b, const Next &next, const LevelW &W, int L,
+                                          int itk, const double *P1, int tpar, const float *Lb, float *Uo,
+                                          int64_t n, double *ipart, float4 *rp_out) {
+    float *const Dw = a.D + b * a.VS;
+    const bool first_of_level = itk == 1;
+    const bool bo_mode = !(L == 0 && first_of_level);
+    const bool same = !(first_of_level && L > 0);
+    TabV To = W.T;   // first iteration of a level > 0: the old field's row tables
+    int ncxo = W.ncx;
+    if (!same) {
+        const DevLevel &lo = a.lvs->lv[L - 1];
+        To.wx = reinterpret_cast<const float4 *>(lo.ax[0].w);
+        To.bx = lo.ax[0].base;
+        ncxo = lo.ax[0].ncp;
+    }
+    float *const Tg0 = a.Tg + (size_t)b * 2 * a.tcap;   // T windows of the last two fields
+    float *const Tgn = Tg0 + (size_t)(tpar ^ 1) * a.tcap;
+    const float *const Tgo = Tg0 + (size_t)tpar * a.tcap;
+    const PcMap pm = pc_map(n, 256);   // (eval_item's PC layout argument: unused here)
+    for (;;) {
+        const int item = next();
+        if (item < 0) break;
+        Item it;
+        if (!study_item(it, a, b, item)) {
+            if ((threadIdx.x & 63) == 0) {
+                ipart[2 * item] = 0.0;
+                ipart[2 * item + 1] = 0.0;
+                rp_out[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
+            }
+            continue;
+        }
+#define ST_EVAL(S, CM) eval_item<S, CM>(it, item, a.Z, a.CZ, W.T, To, W.ncx, W.ncy, ncxo, P1, Tgn, Tgo, bo_mode, \
+                                        Lb, Uo, Dw, n, ipart, rp_out, pm)
+        if (a.conv_mode == 0) {
+            if (same) ST_EVAL(true, 0);
+            else ST_EVAL(false, 0);
+        } else {
+            if (same) ST_EVAL(true, 1);
+            else ST_EVAL(false, 1);
+        }
+#undef ST_EVAL
+    }
+}
+
+// exact subdivision of the lattice for the next level; scr: two lattices of nl_max floats
+__device__ __forceinline__ void refine_lattice(float *lat, char *scr, int ncx, int ncy, int ncz, int nl_max) {
+    float *T1 = reinterpret_cast<float *>(scr), *T2 = T1 + nl_max;
+    refine_axis_st(lat, T1, ncx, ncy, ncz, 0);
+    __syncthreads();
+    refine_axis_st(T1, T2, 2 * ncx - 3, ncy, ncz, 1);
+    __syncthreads();
+    refine_axis_st(T2, lat, 2 * ncx - 3, 2 * ncy - 3, ncz, 2);
+    __syncthreads();
+}
+
+// n < 2, no fit: zero field (output = input), no iterations (one workgroup writes)
+__device__ __forceinline__ void study_empty_exit(const StudyArgs &a, int64_t b, N4State *stb, int p1last) {
+    const int t = threadIdx.x;
+    for (int e = t; e < p1last; e += ST_TPB) a.P1out[b * a.q2cap + e] = 0.0;
+    if (t < VH_MAX_LEVELS) {
+        stb->iters_level[t] = 0;
+        stb->conv_level[t] = 0.0f;
+    }
+    if (t == 0) stb->t_end = wall_clock64();
+}
+
+// the ring of this wave's finished control rows in the fit scratch
+__device__ __forceinline__ FitRing study_ring(const StudyArgs &a, char *scr) {
+    FitRing ring;
+    ring.q = reinterpret_cast<double *>(scr + a.o_wave) + (size_t)(threadIdx.x >> 6) * a.nb_ring * a.s_cap;
+    ring.sx = nullptr;
+    ring.rowcap = a.s_cap;
+    ring.nr = 0;
+    return ring;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the kernel: one workgroup per study
 // ---------------------------------------------------------------------------------------------
-// 4 waves per SIMD (<= 128 VGPRs): one 1024-thread workgroup or two 512-thread ones per CU
+// 4 waves per SIMD (<= 128 VGPRs): one workgroup per CU
 __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t b = a.vol0 + (a.order ? a.order[blockIdx.x] : (int32_t)blockIdx.x);
@@ -605,43 +976,19 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
     }
     const DevLevel &lvl = a.lvs->lv[a.nlev - 1];
     const int p1last = lvl.ax[0].ncp * lvl.ax[1].ncp * a.Z;
-    if (n < 2) {   // no fit: zero field (output = input), no iterations
-        for (int e = t; e < p1last; e += ST_TPB) a.P1out[b * a.q2cap + e] = 0.0;
-        if (t < VH_MAX_LEVELS) {
-            stb->iters_level[t] = 0;
-            stb->conv_level[t] = 0.0f;
-        }
-        if (t == 0) stb->t_end = wall_clock64();
+    if (n < 2) {
+        study_empty_exit(a, b, stb, p1last);
         return;
     }
-    Grp g;
-    g.w = wv;
-    g.nw = ST_WAVES;
-    g.t = t;
-    g.n = ST_TPB;
     float *Lb = a.L0 + b * a.VS;
-    const int64_t fm = a.sc[b].first_masked;
     // fit scratch: lattice numerator (fixed point), then per-wave Q / S rows; from the lattice
     // update to the end of eval: the new field's P1
     unsigned long long *numfix = reinterpret_cast<unsigned long long *>(scr);
     double *const P1 = reinterpret_cast<double *>(scr);
     double *const den = a.den + b * a.lat_cap;          // this level's fit denominators
-    float *const Tg0 = a.Tg + (size_t)b * 2 * a.tcap;   // T windows of the last two fields
-    FitRing ring;
-    ring.q = reinterpret_cast<double *>(scr + a.o_wave) + (size_t)g.w * a.nb_ring * a.s_cap;
-    ring.sx = nullptr;
-    ring.rowcap = a.s_cap;
-    ring.nr = 0;
-    double *const Wk3 = reinterpret_cast<double *>(smem + a.o_wk);
-    // emap scratch: V (= U = NUM), F, DEN, twiddles; the histogram copies in DEN (read by the
-    // series loop, which writes V and F; DEN is written after it)
-    double2 *V = reinterpret_cast<double2 *>(scr), *F = V + ST_FFT_N, *DEN = F + ST_FFT_N;
-    double2 *TW = DEN + ST_FFT_N;
-    unsigned long long *Hc = reinterpret_cast<unsigned long long *>(DEN);
-    static_assert(sizeof(unsigned long long) * ST_HC * VH_MAX_BINS <= sizeof(double2) * ST_FFT_N,
-                  "histogram copies fit the DEN buffer");
-    const PcMap pm = pc_map(n, 256);   // (eval_item's PC layout argument: unused here)
-    const int bins = a.bins;
+    FitRing ring = study_ring(a, scr);
+    const EmapW EW = emap_w(scr);
+    const auto next = [&] { return next_item(M, ordr, a.nitems); };
 #ifdef ST_PROF
     const int st_pt = 0;   // the thread that keeps the marks
 #endif
@@ -653,37 +1000,9 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         M.pc_fb = 0;
         M.pc_pre = 0;
     }
-    if (wv == 0) find_first(a, b, fm, M);
-    {   // item schedule: items by row count, largest first (ties by index), so the dynamic item
-        // queue of every pass ends on small items; the item order of every reduction is unchanged
-        int32_t *isz = reinterpret_cast<int32_t *>(scr);
-        for (int item = wv; item < a.nitems; item += ST_WAVES) {
-            Item it;
-            const bool any = study_item(it, a, b, item);
-            if (lane == 0) isz[item] = any ? it.xe - it.xs + 1 : 0;
-        }
-        __syncthreads();
-        for (int i = t; i < a.nitems; i += ST_TPB) {
-            const int si = isz[i];
-            int rank = 0;
-            for (int j = 0; j < a.nitems; ++j) {
-                const int sj = isz[j];
-                rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-            }
-            ordr[rank] = i;
-        }
-    }
-    __syncthreads();
-    for (;;) {   // L0, U = L0 (U buffer 0) and its range
-        const int item = next_item(M, ordr, a.nitems);
-        if (item < 0) break;
-        Item it;
-        if (!study_item(it, a, b, item)) {
-            if (lane == 0) rpart0[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
-            continue;
-        }
-        init_item(a, b, it, item, Lb, a.U + b * a.VS, n, rpart0);
-    }
+    if (wv == 0) find_first(a, b, a.sc[b].first_masked, M);
+    study_item_order(a, b, reinterpret_cast<int32_t *>(scr), ordr);
+    init_pass(a, b, next, Lb, n, rpart0);
     // every wave must have left the init queue before thread 0 resets the item counter for the
     // denominator pass (a late wave would otherwise take den-pass items)
     __syncthreads();
@@ -693,381 +1012,100 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         for (int e = t; e < nl0; e += ST_TPB) lat[e] = 0.0f;
     }
 #ifdef ST_PROF
-    unsigned long long st_prof[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = clock64();
+    unsigned long long st_prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = clock64();
     if (t == 0) M.fprof[0] = M.fprof[1] = M.fprof[2] = M.fprof[3] = 0ull;
-    if (t == 0) M.sprof[0] = M.sprof[1] = M.sprof[2] = M.sprof[3] = 0ull;
 #endif
     int tpar = 0;   // Tg buffer of the last computed field's T windows
     for (int L = 0; L < a.nlev; ++L) {
-        const DevLevel &lv = a.lvs->lv[L];
-        char *tabp = smem + a.o_tab;
-        load_tables(tab_w(tabp, a.R, a.C, a.Z, a.kcap), lv, a.R, a.C, a.Z);
-        const TabV T = tab_view(tabp, a.R, a.C, a.Z, a.kcap);
-        const int ncx = lv.ax[0].ncp, ncy = lv.ax[1].ncp, ncz = lv.ax[2].ncp;
-        const int nlat = ncx * ncy * ncz;
-        double *const Wk2 = Wk3 + (size_t)ncz * a.Z;
-        for (int e = t; e < ncz * a.Z; e += ST_TPB) {   // dense slice weights of this level
-            Wk3[e] = lv.wk3[e];
-            Wk2[e] = lv.wk2[e];
-        }
-        double2 *const Wx3 = reinterpret_cast<double2 *>(smem + a.o_wx), *const Wx2 = Wx3 + 2 * a.R;
-        for (int x = t; x < a.R; x += ST_TPB) {   // row weights of this level (wave-uniform reads)
-            const double2 *w3 = reinterpret_cast<const double2 *>(lv.ax[0].w3i + 4 * x);
-            const double2 *w2 = reinterpret_cast<const double2 *>(lv.ax[0].w2 + 4 * x);
-            Wx3[2 * x] = w3[0];
-            Wx3[2 * x + 1] = w3[1];
-            Wx2[2 * x] = w2[0];
-            Wx2[2 * x + 1] = w2[1];
-        }
-        // ---- denominator of this level: sum of w^2 over the mask (the compute waves' rings) ----
-        for (int e = t; e < 2 * nlat; e += ST_TPB) numfix[e] = 0ull;
-        if (t == 0) M.item_ctr = 0;
-        __syncthreads();
-        {
-            const int uin = M.uin;
-            float *const Ub = a.U + uin * a.half + b * a.VS;
-            for (;;) {
-                const int item = next_item(M, ordr, a.nitems);
-                if (item < 0) break;
-                Item it;
-                if (!study_item(it, a, b, item)) continue;
-                fit_item<1, true>(it, T, Wk2, Wx2, ncy, ncz, a.Z, bins, Ub, n, sE, 0.0f, 1.0, ring,
-                                  a.nb_ring, numfix);
-            }
-        }
-        __syncthreads();
+        const LevelW W = level_begin(a, a.lvs->lv[L], smem);
+        // ---- denominator of this level: sum of w^2 over the mask ----
+        fit_pass<1>(a, b, M, next, W, a.U + M.uin * a.half + b * a.VS, n, sE, 0.0f, 1.0, ring, numfix);
         ST_MARK(0);
-        for (int e = t; e < nlat; e += ST_TPB) den[e] = fix128_get(numfix + 2 * e, numfix + 2 * e + 1);
-        {
-            // ---- the iterations ----
-            int itn = 0;       // iterations computed in this level
-            int uin = M.uin;   // U buffer (and its rpart row) of the last computed iteration
-            for (;;) {
-                gsync(g, M);
-                ST_MARK(10);
-                float *const Ub = a.U + uin * a.half + b * a.VS;
-                const float4 *const rp_in = rpart0 + uin * a.nitems;
-                if (g.w == 0) {   // ctrl: ITK's while-condition (at the cap, or conv_mode 1), bin range
-                    Range3 r;
-                    r3_init(r);
-                    for (int i = lane; i < a.nitems; i += 64) {
-                        const float4 p = rp_in[i];
-                        Range3 o;
-                        o.mx = p.x; o.m1 = p.y; o.m2 = p.z; o.m3 = p.w;
-                        r3_merge(r, o);
-                    }
-                    r = r3_wave(r);
-                    if (lane < M.nfirst) M.fu[lane] = Ub[M.foff[lane]];   // the run's values
-                    wave_lds_order();
-                    if (lane == 0) {
-                        M.stop = 0;
-                        M.exact = 0;
-                        if (itn > 0) {
-                            if (a.conv_mode == 1) M.conv = conv_of(M.sd, M.sd2, (double)n);
-                            if (!(M.conv > (double)a.thresh) || itn >= a.lvs->max_iters[L]) M.stop = 1;
-                        }
-                        if (!M.stop) {
-                            float bmin;
-                            M.bmax = r.mx;
-                            if (r3_bin_min(r, M.fu, M.nfirst, bmin)) {
-                                M.bin_min = bmin;
-                                M.slope = (r.mx - bmin) / (float)(bins - 1);
-                            } else {
-                                M.exact = 1;
-                            }
-                        }
-                    }
+        for (int e = t; e < W.nlat; e += ST_TPB) den[e] = fix128_get(numfix + 2 * e, numfix + 2 * e + 1);
+        int itn = 0;       // iterations computed in this level
+        int uin = M.uin;   // U buffer (and its rpart row) of the last computed iteration
+        for (;;) {
+            __syncthreads();
+            ST_MARK(10);
+            float *const Ub = a.U + uin * a.half + b * a.VS;
+            if (wv == 0)   // the items' ranges; conv_mode 1: the S7x sums of the last eval
+                ctrl_decide(a, M, r3_merge_records(rpart0 + uin * a.nitems, a.nitems), Ub, itn, L, [&] {
+                    return a.conv_mode == 1 ? conv_of(M.sd, M.sd2, (double)n) : M.conv;
+                });
+            __syncthreads();
+            ST_MARK(1);
+            if (M.stop) break;
+            if (M.exact) exact_bin_min(a, b, Ub, scr, M);
+            const int itk = itn + 1;   // the iteration computed now
+            ST_MARK(9);
+            const float bmin = M.bin_min, slope = M.slope;
+            const double rinv = 1.0 / (double)slope;   // div_r form of the bin division
+            hist_slice(Ub, 0, n, EW.Hc, bmin, rinv, a.bins);
+            ST_MARK(2);
+            emap_phase(a, EW, sE, bmin, slope, [&](int h) {   // the four LDS copies' sums
+                unsigned long long s = 0ull;
+                for (int q = 0; q < ST_HC; ++q) {
+                    const unsigned long long w = EW.Hc[q * VH_MAX_BINS + h];
+                    s += (hist_count(w) << 24) - hist_osum(w);
+                    if (h > 0) s += hist_osum(EW.Hc[q * VH_MAX_BINS + h - 1]);
                 }
-                gsync(g, M);
-                ST_MARK(1);
-                if (M.stop) break;
-                if (M.exact) {
-                    float *s_cmax = reinterpret_cast<float *>(scr);
-                    const float m = exact_min_study(a, b, Ub, s_cmax, s_cmax + g.n, g, M);
-                    if (g.t == 0) {
-                        M.bin_min = m;
-                        M.slope = (M.bmax - m) / (float)(bins - 1);
-                    }
-                    gsync(g, M);
-                }
-                const int itk = itn + 1;   // the iteration computed now
-                ST_MARK(9);
-                const float bmin = M.bin_min, slope = M.slope;
-                const double rinv = 1.0 / (double)slope;   // div_r form of the bin division
-                // ---- hist (S3): one packed 64-bit add per value ----
-                for (int i = g.t; i < ST_HC * VH_MAX_BINS; i += g.n) Hc[i] = 0ull;
-                gsync(g, M);
-                {
-                    unsigned long long *H = Hc + (lane & (ST_HC - 1)) * VH_MAX_BINS;
-                    for (int64_t j0 = (int64_t)g.t * 16; j0 < n; j0 += (int64_t)g.n * 16) {
-                        float u[16];
-                        if (j0 + 16 <= n) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float4 v = reinterpret_cast<const float4 *>(Ub + j0)[q];
-                                u[4 * q] = v.x; u[4 * q + 1] = v.y; u[4 * q + 2] = v.z; u[4 * q + 3] = v.w;
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 16; ++k) u[k] = j0 + k < n ? Ub[j0 + k] : __int_as_float(0x7fc00000);
-                        }
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) {
-                            int idx;
-                            const unsigned long long w = hist_pack(u[k], bmin, rinv, bins, idx);
-                            atomicAdd(&H[idx], w);
-                        }
-                    }
-                }
-                gsync(g, M);
-                ST_MARK(2);
-                // ---- emap (same arithmetic as n4.hip k_n4_emap and the oracle) ----
-                {
-                    const int P = VH_FFT_P, off = (P - bins) / 2;
-                    const float sFWHM = a.fwhm / slope;
-                    const float ef = (float)(4.0 * LN2 / (double)(sFWHM * sFWHM));
-                    const float sf = (float)(2.0 * sqrt(LN2 / PI_D) / (double)sFWHM);
-                    // one twiddle per thread: P / 2 <= g.n
+                return s;
+            });
+            ST_MARK(3);
 #ifdef ST_PROF
-                    const unsigned long long sp0 = clock64();
-#endif
-                    const double2 twv = g.t < P / 2 ? a.tw[g.t] : make_double2(0.0, 0.0);   // in flight
-                    for (int i = g.t; i < P; i += g.n) {   // histogram series and Gaussian kernel
-                        const int h = i - off;
-                        unsigned long long s = 0ull;
-                        if (h >= 0 && h < bins)
-                            for (int q = 0; q < ST_HC; ++q) {
-                                const unsigned long long w = Hc[q * VH_MAX_BINS + h];
-                                s += (hist_count(w) << 24) - hist_osum(w);
-                                if (h > 0) s += hist_osum(Hc[q * VH_MAX_BINS + h - 1]);
-                            }
-                        V[fpad(i)] = make_double2((double)s * (1.0 / 16777216.0), 0.0);
-#ifdef ST_PROF
-                        const unsigned long long sp1 = clock64();
-                        if (g.t == 300) M.sprof[1] += sp1 - sp0;
-#endif
-                        double fx;
-                        if (i == 0) {
-                            fx = (double)sf;
-                        } else if (i == P / 2) {
-                            fx = (double)sf * exp(-0.25 * (double)((float)P * (float)P) * (double)ef);
-                        } else {
-                            const float nf = (float)(i < P / 2 ? i : P - i);
-                            fx = (double)(sf * expf_cr_tail(-(nf * nf) * ef));
-                        }
-                        F[fpad(i)] = make_double2(fx, 0.0);
-#ifdef ST_PROF
-                        if (g.t == 300) M.sprof[2] += clock64() - sp1;
-#endif
-                    }
-#ifdef ST_PROF
-                    const unsigned long long sp2 = clock64();
-#endif
-                    if (g.t < P / 2) TW[g.t] = twv;
-#ifdef ST_PROF
-                    if (g.t == 300) M.sprof[0] += clock64() - sp0;
-                    if (g.t == 200) M.sprof[3] += clock64() - sp2;
-#endif
-                    gsync(g, M);
-                    ST_MARK(11);
-                    if (g.w < 2) wave_fft_lds(g.w ? F : V, TW, false, FftId(), FftId());
-                    gsync(g, M);
-                    ST_MARK(12);
-                    const auto wpost = [=](int i, double2 v) {   // clamp; the moment series' points
-                        const double ur = v.x > 0.0 ? v.x : 0.0;
-                        const float c = bmin + ((float)i - (float)off) * slope;
-                        DEN[fpad(i)] = make_double2(ur, 0.0);
-                        return make_double2((double)c * ur, 0.0);
-                    };
-#if ST_WPAR
-                    // Wiener filter on every thread (the divisions would otherwise run 8 deep on
-                    // one wave); the same per-point arithmetic as the gather-side form below
-                    for (int i = g.t; i < P; i += g.n) {
-                        const double2 f = F[fpad(i)], v = V[fpad(i)];
-                        const double fa = f.x, fb = f.y;
-                        const double gg = fa / ((fa * fa - (-fb) * fb) + (double)a.noise);
-                        V[fpad(i)] = make_double2(v.x * gg, v.y * gg);
-                    }
-                    gsync(g, M);
-                    ST_MARK(16);
-#if ST_WPAR >= 2
-                    if (g.w == 0) wave_fft_lds(V, TW, true, FftId(), FftId());   // inverse
-                    ST_MARK(17);
-                    gsync(g, M);
-                    for (int i = g.t; i < P; i += g.n) V[fpad(i)] = wpost(i, V[fpad(i)]);
+            fit_pass<0>(a, b, M, next, W, Ub, n, sE, bmin, rinv, ring, numfix, wv == (st_pt >> 6) ? M.fprof : nullptr);
 #else
-                    if (g.w == 0) wave_fft_lds(V, TW, true, FftId(), wpost);   // inverse, clamp, series
-                    ST_MARK(17);
+            fit_pass<0>(a, b, M, next, W, Ub, n, sE, bmin, rinv, ring, numfix);
 #endif
-#else
-                    if (g.w == 0) {   // Wiener filter (first pass), inverse, clamp and the moment series (last pass)
-                        const double noise = (double)a.noise;
-                        wave_fft_lds(V, TW, true,
-                            [=](int i, double2 v) {
-                                const double2 f = F[fpad(i)];
-                                const double fa = f.x, fb = f.y;
-                                const double gg = fa / ((fa * fa - (-fb) * fb) + noise);
-                                return make_double2(v.x * gg, v.y * gg);
-                            }, wpost);
-                    }
-#endif
-                    gsync(g, M);
-                    ST_MARK(13);
-                    const auto kmul = [=](int i, double2 v) {   // times the kernel's transform
-                        const double2 f = F[fpad(i)];
-                        const double fa = f.x, fb = f.y;
-                        return make_double2(v.x * fa - v.y * fb, v.x * fb + v.y * fa);
-                    };
-#if ST_WPAR >= 3
-                    // each series: forward; the product on every thread; inverse
-                    if (g.w < 2) wave_fft_lds(g.w ? DEN : V, TW, false, FftId(), FftId());
-                    gsync(g, M);
-                    for (int e = g.t; e < 2 * P; e += g.n) {
-                        double2 *const x = e < P ? V : DEN;
-                        const int i = e < P ? e : e - P;
-                        x[fpad(i)] = kmul(i, x[fpad(i)]);
-                    }
-                    gsync(g, M);
-                    if (g.w < 2) wave_fft_lds(g.w ? DEN : V, TW, true, FftId(), FftId());
-#else
-                    if (g.w < 2) {   // each series: forward, times the kernel's transform (last pass), inverse
-                        double2 *x = g.w ? DEN : V;
-                        wave_fft_lds(x, TW, false, FftId(), kmul);
-                        wave_fft_lds(x, TW, true, FftId(), FftId());
-                    }
-#endif
-                    gsync(g, M);
-                    ST_MARK(14);
-                    for (int i = g.t; i < bins; i += g.n) {
-                        const double d = DEN[fpad(i + off)].x;
-                        sE[i] = d != 0.0 ? (float)(V[fpad(i + off)].x / d) : 0.0f;
-                    }
-                    gsync(g, M);
+            ST_MARK(4);
+            // ---- lattice update and P1 (in the fit scratch, free from here to the end of eval) ----
+            lattice_update(lat, W.nlat, [&](int e) { return den[e]; },
+                           [&](int e) { return fix128_get(numfix + 2 * e, numfix + 2 * e + 1); });
+            __syncthreads();
+            p1_from_lattice(lat, W.T, W.ncx * W.ncy, W.ncz, a.Z, P1);
+            if (t == 0) M.item_ctr = 0;
+            __syncthreads();
+            ST_MARK(5);
+            // ---- eval: U into the other buffer, d into D, this field's T windows into Tg ----
+            const int uo = (uin + 1) % ST_NB;
+            eval_pass(a, b, next, W, L, itk, P1, tpar, Lb, a.U + uo * a.half + b * a.VS, n, ipart,
+                      rpart0 + uo * a.nitems);
+            __syncthreads();
+            ST_MARK(6);
+            if (a.conv_mode == 0) {   // S7 on the whole workgroup by guess and verify
+                PcShared<ST_TPB> &PW = *reinterpret_cast<PcShared<ST_TPB> *>(smem + a.o_scr);
+                const float *const Dr = a.D + b * a.VS;
+                // the raster d buffer is free once pass 0 has read it: PCX's stored increments
+                // below the iteration cap this iteration's measure only decides whether the
+                // level goes on: PC may certify "above the threshold" without the exact sig
+                pcw_run<ST_TPB, ST_EVAL_EXP>([=](int64_t r) { return Dr[r]; }, a.D + a.half + b * a.VS, n, PW, M.ch, itk,
+                        reinterpret_cast<double *>(a.D + b * a.VS), (int)(a.VS / 2),
+                        itk < a.lvs->max_iters[L] ? a.thresh : 0.0f,
+                        a.pcdrift ? a.pcdrift + (size_t)b * ST_TPB : nullptr, !(L == 0 && itk == 1),
+                        itk == 1 || M.pc_pre != 0);   // early decision: a level's first call, then while it decides
+                if (t == 0) {
+                    M.pc_pre = PW.xdone == 4 * itk + 1;
+                    M.conv = (double)M.ch.conv;
+                    M.pc_rounds += PW.rounds;
+                    // serial fallbacks of the exact rounds (units), frozen-serial stage-0 closes (thousands)
+                    M.pc_fb += (PW.fallback == 4 * itk + 2 ? 1 : 0) + 1000 * PW.nfrz;
                 }
-                ST_MARK(3);
-                // ---- fit ----
-                for (int e = g.t; e < 2 * nlat; e += g.n) numfix[e] = 0ull;
-                if (g.t == 0) M.item_ctr = 0;
-                gsync(g, M);
-                for (;;) {
-                    const int item = next_item(M, ordr, a.nitems);
-                    if (item < 0) break;
-                    Item it;
-                    if (!study_item(it, a, b, item)) continue;
-                    fit_item<0, true>(it, T, Wk3, Wx3, ncy, ncz, a.Z, bins, Ub, n, sE, bmin, rinv, ring,
-                                      a.nb_ring, numfix
-#ifdef ST_PROF
-                                      , (t >> 6) == (st_pt >> 6) ? M.fprof : nullptr
-#endif
-                                      );
+            } else if (wv == 0) {   // S7x
+                double sd, sd2;
+                s7x_sums(ipart, a.nitems, sd, sd2);
+                if (lane == 0) {
+                    M.sd = sd;
+                    M.sd2 = sd2;
                 }
-                gsync(g, M);
-                ST_MARK(4);
-                // ---- lattice update and P1 (in the fit scratch, free from here to the end of eval) ----
-                for (int e = g.t; e < nlat; e += g.n) {
-                    const double d = den[e];
-                    const double num = fix128_get(numfix + 2 * e, numfix + 2 * e + 1);
-                    const float phi = d != 0.0 ? (float)(num / d) : 0.0f;
-                    lat[e] += phi;
-                }
-                gsync(g, M);
-                for (int e = g.t; e < ncx * ncy * a.Z; e += g.n) {
-                    const int ij = e / a.Z, z = e % a.Z;
-                    const float4 w = T.wz[z];
-                    const float *l = lat + ij * ncz + T.bz[z];
-                    P1[e] = (double)w.x * (double)l[0] + (double)w.y * (double)l[1] +
-                            (double)w.z * (double)l[2] + (double)w.w * (double)l[3];
-                }
-                if (g.t == 0) M.item_ctr = 0;
-                gsync(g, M);
-                ST_MARK(5);
-                // ---- eval: U into the other buffer, d into D, this field's T windows into Tg ----
-                {
-                    const int uo = (uin + 1) % ST_NB;
-                    float *const Uo = a.U + uo * a.half + b * a.VS;
-                    float *const Dw = a.D + b * a.VS;
-                    float4 *const rp_out = rpart0 + uo * a.nitems;
-                    const bool first_of_level = itk == 1;
-                    const bool bo_mode = !(L == 0 && first_of_level);
-                    const bool same = !(first_of_level && L > 0);
-                    TabV To = T;   // first iteration of a level > 0: the old field's row tables
-                    int ncxo = ncx;
-                    if (!same) {
-                        const DevLevel &lo = a.lvs->lv[L - 1];
-                        To.wx = reinterpret_cast<const float4 *>(lo.ax[0].w);
-                        To.bx = lo.ax[0].base;
-                        ncxo = lo.ax[0].ncp;
-                    }
-                    float *const Tgn = Tg0 + (size_t)(tpar ^ 1) * a.tcap;
-                    const float *const Tgo = Tg0 + (size_t)tpar * a.tcap;
-                    for (;;) {
-                        const int item = next_item(M, ordr, a.nitems);
-                        if (item < 0) break;
-                        Item it;
-                        if (!study_item(it, a, b, item)) {
-                            if (lane == 0) {
-                                ipart[2 * item] = 0.0;
-                                ipart[2 * item + 1] = 0.0;
-                                rp_out[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
-                            }
-                            continue;
-                        }
-#define ST_EVAL(S, CM) eval_item<S, CM>(it, item, a.Z, a.CZ, T, To, ncx, ncy, ncxo, P1, Tgn, Tgo, bo_mode, \
-                                        Lb, Uo, Dw, n, ipart, rp_out, pm)
-                        if (a.conv_mode == 0) {
-                            if (same) ST_EVAL(true, 0);
-                            else ST_EVAL(false, 0);
-                        } else {
-                            if (same) ST_EVAL(true, 1);
-                            else ST_EVAL(false, 1);
-                        }
-#undef ST_EVAL
-                    }
-                }
-                gsync(g, M);
-                ST_MARK(6);
-                if (a.conv_mode == 0) {   // S7 on the whole workgroup by guess and verify
-                    PcShared<ST_TPB> &PW = *reinterpret_cast<PcShared<ST_TPB> *>(smem + a.o_scr);
-                    const float *const Dr = a.D + b * a.VS;
-                    // the raster d buffer is free once pass 0 has read it: PCX's stored increments
-                    // below the iteration cap this iteration's measure only decides whether the
-                    // level goes on: PC may certify "above the threshold" without the exact sig
-                    pcw_run<ST_TPB, ST_EVAL_EXP>([=](int64_t r) { return Dr[r]; }, a.D + a.half + b * a.VS, n, PW, M.ch, itk,
-                            reinterpret_cast<double *>(a.D + b * a.VS), (int)(a.VS / 2),
-                            itk < a.lvs->max_iters[L] ? a.thresh : 0.0f,
-                            a.pcdrift ? a.pcdrift + (size_t)b * ST_TPB : nullptr, !(L == 0 && itk == 1),
-                            itk == 1 || M.pc_pre != 0);   // early decision: a level's first call, then while it decides
-                    if (t == 0) {
-                        M.pc_pre = PW.xdone == 4 * itk + 1;
-                        M.conv = (double)M.ch.conv;
-                        M.pc_rounds += PW.rounds;
-                        // serial fallbacks of the exact rounds (units), frozen-serial stage-0 closes (thousands)
-                        M.pc_fb += (PW.fallback == 4 * itk + 2 ? 1 : 0) + 1000 * PW.nfrz;
-                    }
-                } else if (g.w == 0) {   // S7x: item partials in item order
-                    double sd = 0.0, sd2 = 0.0;
-                    for (int i = lane; i < a.nitems; i += 64) {
-                        sd += ipart[2 * i];
-                        sd2 += ipart[2 * i + 1];
-                    }
-                    for (int off = 32; off > 0; off >>= 1) {
-                        sd += __shfl_down(sd, off, 64);
-                        sd2 += __shfl_down(sd2, off, 64);
-                    }
-                    if (lane == 0) {
-                        M.sd = sd;
-                        M.sd2 = sd2;
-                    }
-                }
-                ST_MARK(7);
-                tpar ^= 1;
-                uin = (uin + 1) % ST_NB;
-                itn = itk;
             }
-            if (g.t == 0) {
-                M.itn = itn;
-                M.uin = uin;
-            }
+            ST_MARK(7);
+            tpar ^= 1;
+            uin = uo;
+            itn = itk;
+        }
+        if (t == 0) {
+            M.itn = itn;
+            M.uin = uin;
         }
         __syncthreads();
         ST_MARK(8);
@@ -1075,16 +1113,8 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
             stb->iters_level[L] = M.itn;
             stb->conv_level[L] = (float)M.conv;
         }
-        if (L < a.nlev - 1) {   // exact subdivision of the lattice for the next level
-            const int nl_max = lvl.ax[0].ncp * lvl.ax[1].ncp * lvl.ax[2].ncp;
-            float *T1 = reinterpret_cast<float *>(scr), *T2 = T1 + nl_max;
-            refine_axis_st(lat, T1, ncx, ncy, ncz, 0);
-            __syncthreads();
-            refine_axis_st(T1, T2, 2 * ncx - 3, ncy, ncz, 1);
-            __syncthreads();
-            refine_axis_st(T2, lat, 2 * ncx - 3, 2 * ncy - 3, ncz, 2);
-            __syncthreads();
-        }
+        if (L < a.nlev - 1)
+            refine_lattice(lat, scr, W.ncx, W.ncy, W.ncz, lvl.ax[0].ncp * lvl.ax[1].ncp * lvl.ax[2].ncp);
     }
 #ifdef ST_PROF
     // ST_PROF_B: the study whose phase cycles are printed (one study: a printf in every workgroup
@@ -1096,29 +1126,16 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         int its = 0;   // (st_pt is thread 0, the writer of iters_level)
         for (int q = 0; q < a.nlev; ++q) its += stb->iters_level[q];
         printf("ST_PROF b %d n %lld its %d den %llu ctrl %llu hist %llu emap %llu fit %llu latP1 %llu eval %llu "
-               "wait %llu level %llu exact %llu top %llu | emap: series %llu fwd %llu filter %llu conv %llu div %llu"
-               " (filter: wiener %llu fft %llu sync %llu)\n",
-               ST_PROF_B, (long long)n, its, st_prof[0], st_prof[1], st_prof[2],
-               st_prof[3] + st_prof[11] + st_prof[12] + st_prof[13] + st_prof[14],
-               st_prof[4], st_prof[5], st_prof[6], st_prof[7], st_prof[8], st_prof[9], st_prof[10],
-               st_prof[11], st_prof[12], st_prof[13] + st_prof[16] + st_prof[17], st_prof[14], st_prof[3],
-               st_prof[16], st_prof[17], st_prof[13]);
-        printf("ST_PROF fit: rows %llu push %llu contract %llu items %llu | series thread 300: total %llu "
-               "hist %llu kernel-exp %llu; thread 200 twiddle %llu\n", M.fprof[0], M.fprof[1],
-               M.fprof[2], M.fprof[3], M.sprof[0], M.sprof[1], M.sprof[2], M.sprof[3]);
+               "wait %llu level %llu exact %llu top %llu\n",
+               ST_PROF_B, (long long)n, its, st_prof[0], st_prof[1], st_prof[2], st_prof[3],
+               st_prof[4], st_prof[5], st_prof[6], st_prof[7], st_prof[8], st_prof[9], st_prof[10]);
+        printf("ST_PROF fit: rows %llu push %llu contract %llu items %llu\n", M.fprof[0], M.fprof[1],
+               M.fprof[2], M.fprof[3]);
     }
 #endif
-    {   // final field's P1 for k_n4_final, from the lattice (the last level's tables are loaded)
-        const TabV T = tab_view(smem + a.o_tab, a.R, a.C, a.Z, a.kcap);
-        const int ncz = lvl.ax[2].ncp;
-        for (int e = t; e < p1last; e += ST_TPB) {
-            const int ij = e / a.Z, z = e % a.Z;
-            const float4 w = T.wz[z];
-            const float *l = lat + ij * ncz + T.bz[z];
-            a.P1out[b * a.q2cap + e] = (double)w.x * (double)l[0] + (double)w.y * (double)l[1] +
-                                       (double)w.z * (double)l[2] + (double)w.w * (double)l[3];
-        }
-    }
+    // final field's P1 for k_n4_final, from the lattice (the last level's tables are loaded)
+    p1_from_lattice(lat, tab_view(smem + a.o_tab, a.R, a.C, a.Z, a.kcap), lvl.ax[0].ncp * lvl.ax[1].ncp,
+                    lvl.ax[2].ncp, a.Z, a.P1out + b * a.q2cap);
     if (t == 0) {
         stb->conv = M.conv;
         stb->active = 0;
@@ -1127,6 +1144,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         stb->t_end = wall_clock64();
     }
 }
+
 
 // =============================================================================================
 // Grid form (round 6): ONE study over G cooperating workgroups (k_n4_studyg, a cooperative launch)
@@ -1190,10 +1208,7 @@ __device__ void publish_range(const StudyGrid &g, const float4 *rp, const int32_
     for (int c = lane;; c += 64) {
         const int k = owned_item(c, r, G, nitems);
         if (k < 0) break;
-        const float4 p = rp[ordr[k]];
-        Range3 o;
-        o.mx = p.x; o.m1 = p.y; o.m2 = p.z; o.m3 = p.w;
-        r3_merge(rg, o);
+        r3_merge(rg, r3_of(rp[ordr[k]]));
     }
     rg = r3_wave(rg);
     if (lane == 0) g.rrec[(size_t)u * G + r] = make_float4(rg.mx, rg.m1, rg.m2, rg.m3);
@@ -1211,7 +1226,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ Pcg2Lds PL;
     const int64_t b = a.vol0;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, wv = t >> 6;
     const int r = blockIdx.x, G = gridDim.x;
     StudyMisc &M = *reinterpret_cast<StudyMisc *>(smem + a.o_misc);
     float *sE = reinterpret_cast<float *>(smem + a.o_E);
@@ -1230,75 +1245,26 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
     }
     const DevLevel &lvl = a.lvs->lv[a.nlev - 1];
     const int p1last = lvl.ax[0].ncp * lvl.ax[1].ncp * a.Z;
-    if (n < 2) {   // no fit: zero field, no iterations (uniform over the grid)
-        if (r == 0) {
-            for (int e = t; e < p1last; e += ST_TPB) a.P1out[b * a.q2cap + e] = 0.0;
-            if (t < VH_MAX_LEVELS) {
-                stb->iters_level[t] = 0;
-                stb->conv_level[t] = 0.0f;
-            }
-            if (t == 0) stb->t_end = wall_clock64();
-        }
+    if (n < 2) {   // (uniform over the grid)
+        if (r == 0) study_empty_exit(a, b, stb, p1last);
         kst_end(gd.pc.kst);
         return;
     }
-    Grp g;
-    g.w = wv;
-    g.nw = ST_WAVES;
-    g.t = t;
-    g.n = ST_TPB;
     float *Lb = a.L0 + b * a.VS;
-    const int64_t fm = a.sc[b].first_masked;
     unsigned long long *numfix = reinterpret_cast<unsigned long long *>(scr);
     double *const P1 = reinterpret_cast<double *>(scr);
-    float *const Tg0 = a.Tg + (size_t)b * 2 * a.tcap;
-    FitRing ring;
-    ring.q = reinterpret_cast<double *>(scr + a.o_wave) + (size_t)g.w * a.nb_ring * a.s_cap;
-    ring.sx = nullptr;
-    ring.rowcap = a.s_cap;
-    ring.nr = 0;
-    double *const Wk3 = reinterpret_cast<double *>(smem + a.o_wk);
-    double2 *V = reinterpret_cast<double2 *>(scr), *F = V + ST_FFT_N, *DEN = F + ST_FFT_N;
-    double2 *TW = DEN + ST_FFT_N;
-    unsigned long long *Hc = reinterpret_cast<unsigned long long *>(DEN);
-    const PcMap pm = pc_map(n, 256);
-    const int bins = a.bins;
+    FitRing ring = study_ring(a, scr);
+    const EmapW EW = emap_w(scr);
+    const auto next = [&] { return next_item_g(M, ordr, a.nitems, r, G); };   // this workgroup's items
     unsigned long long *const NSd = gd.nsum + (size_t)2 * 2 * a.lat_cap;   // denominators
 
     if (t == 0) {
         M.item_ctr = 0;
         M.uin = 0;
     }
-    if (wv == 0) find_first(a, b, fm, M);
-    {   // the largest-first item order (every workgroup computes the same one)
-        int32_t *isz = reinterpret_cast<int32_t *>(scr);
-        for (int item = wv; item < a.nitems; item += ST_WAVES) {
-            Item it;
-            const bool any = study_item(it, a, b, item);
-            if (lane == 0) isz[item] = any ? it.xe - it.xs + 1 : 0;
-        }
-        __syncthreads();
-        for (int i = t; i < a.nitems; i += ST_TPB) {
-            const int si = isz[i];
-            int rank = 0;
-            for (int j = 0; j < a.nitems; ++j) {
-                const int sj = isz[j];
-                rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-            }
-            ordr[rank] = i;
-        }
-    }
-    __syncthreads();
-    for (;;) {   // L0, U = L0 (U buffer 0) and its range, this workgroup's items
-        const int item = next_item_g(M, ordr, a.nitems, r, G);
-        if (item < 0) break;
-        Item it;
-        if (!study_item(it, a, b, item)) {
-            if (lane == 0) rpart0[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
-            continue;
-        }
-        init_item(a, b, it, item, Lb, a.U + b * a.VS, n, rpart0);
-    }
+    if (wv == 0) find_first(a, b, a.sc[b].first_masked, M);
+    study_item_order(a, b, reinterpret_cast<int32_t *>(scr), ordr);   // (every workgroup the same one)
+    init_pass(a, b, next, Lb, n, rpart0);
     __syncthreads();
     publish_range(gd, rpart0, ordr, a.nitems, 0, r, G);
     {
@@ -1312,345 +1278,116 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
     uint64_t stg_p[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stg_t0 = wall_clock64();
 #endif
     for (int L = 0; L < a.nlev; ++L) {
-        const DevLevel &lv = a.lvs->lv[L];
-        char *tabp = smem + a.o_tab;
-        load_tables(tab_w(tabp, a.R, a.C, a.Z, a.kcap), lv, a.R, a.C, a.Z);
-        const TabV T = tab_view(tabp, a.R, a.C, a.Z, a.kcap);
-        const int ncx = lv.ax[0].ncp, ncy = lv.ax[1].ncp, ncz = lv.ax[2].ncp;
-        const int nlat = ncx * ncy * ncz;
-        double *const Wk2 = Wk3 + (size_t)ncz * a.Z;
-        for (int e = t; e < ncz * a.Z; e += ST_TPB) {
-            Wk3[e] = lv.wk3[e];
-            Wk2[e] = lv.wk2[e];
-        }
-        double2 *const Wx3 = reinterpret_cast<double2 *>(smem + a.o_wx), *const Wx2 = Wx3 + 2 * a.R;
-        for (int x = t; x < a.R; x += ST_TPB) {
-            const double2 *w3 = reinterpret_cast<const double2 *>(lv.ax[0].w3i + 4 * x);
-            const double2 *w2 = reinterpret_cast<const double2 *>(lv.ax[0].w2 + 4 * x);
-            Wx3[2 * x] = w3[0];
-            Wx3[2 * x + 1] = w3[1];
-            Wx2[2 * x] = w2[0];
-            Wx2[2 * x + 1] = w2[1];
-        }
+        const LevelW W = level_begin(a, a.lvs->lv[L], smem);
         // ---- denominators of this level: the previous level's are read by nobody any more (every
         // workgroup passed the last iteration's barriers); level 0's were zeroed by the host ----
         if (L > 0) {
-            for (int e = r * ST_TPB + t; e < 2 * nlat; e += G * ST_TPB) NSd[e] = 0ull;
+            for (int e = r * ST_TPB + t; e < 2 * W.nlat; e += G * ST_TPB) NSd[e] = 0ull;
             grid.sync();
         }
-        for (int e = t; e < 2 * nlat; e += ST_TPB) numfix[e] = 0ull;
-        if (t == 0) M.item_ctr = 0;
-        __syncthreads();
-        {
-            float *const Ub = a.U + M.uin * a.half + b * a.VS;
-            for (;;) {
-                const int item = next_item_g(M, ordr, a.nitems, r, G);
-                if (item < 0) break;
-                Item it;
-                if (!study_item(it, a, b, item)) continue;
-                fit_item<1, true>(it, T, Wk2, Wx2, ncy, ncz, a.Z, bins, Ub, n, sE, 0.0f, 1.0, ring,
-                                  a.nb_ring, numfix);
-            }
-        }
-        __syncthreads();
-        for (int e = t; e < nlat; e += ST_TPB) fix128_flush(NSd + 2 * e, NSd + 2 * e + 1, numfix[2 * e], numfix[2 * e + 1]);
+        fit_pass<1>(a, b, M, next, W, a.U + M.uin * a.half + b * a.VS, n, sE, 0.0f, 1.0, ring, numfix);
+        for (int e = t; e < W.nlat; e += ST_TPB) fix128_flush(NSd + 2 * e, NSd + 2 * e + 1, numfix[2 * e], numfix[2 * e + 1]);
         grid.sync();
         STG_MARK(7);
-        {
-            int itn = 0;
-            int uin = M.uin;
-            for (;;) {
-                float *const Ub = a.U + uin * a.half + b * a.VS;
-                const int p = gi & 1;
-                unsigned long long *const HS = gd.hsum + (size_t)p * 2 * VH_MAX_BINS;
-                unsigned long long *const HSo = gd.hsum + (size_t)(p ^ 1) * 2 * VH_MAX_BINS;
-                unsigned long long *const NS = gd.nsum + (size_t)p * 2 * a.lat_cap;
-                unsigned long long *const NSo = gd.nsum + (size_t)(p ^ 1) * 2 * a.lat_cap;
-                if (g.w == 0) {   // ctrl (every workgroup, the same decision): the grid's records
-                    Range3 rr;
-                    r3_init(rr);
-                    for (int i = lane; i < G; i += 64) {
-                        const float4 q = gd.rrec[(size_t)uin * G + i];
-                        Range3 o;
-                        o.mx = q.x; o.m1 = q.y; o.m2 = q.z; o.m3 = q.w;
-                        r3_merge(rr, o);
-                    }
-                    rr = r3_wave(rr);
-                    if (lane < M.nfirst) M.fu[lane] = Ub[M.foff[lane]];
-                    double sd = 0.0, sd2 = 0.0;   // S7x: the item sums in item order (k_n4_study's order)
-                    if (a.conv_mode == 1 && itn > 0) {
-                        for (int i = lane; i < a.nitems; i += 64) {
-                            sd += gd.ipart[2 * i];
-                            sd2 += gd.ipart[2 * i + 1];
-                        }
-                        for (int off = 32; off > 0; off >>= 1) {
-                            sd += __shfl_down(sd, off, 64);
-                            sd2 += __shfl_down(sd2, off, 64);
-                        }
-                    }
-                    wave_lds_order();
-                    if (lane == 0) {
-                        M.stop = 0;
-                        M.exact = 0;
-                        if (itn > 0) {
-                            M.conv = a.conv_mode == 1 ? conv_of(sd, sd2, (double)n) : (double)stb->conv_w;
-                            if (!(M.conv > (double)a.thresh) || itn >= a.lvs->max_iters[L]) M.stop = 1;
-                        }
-                        if (!M.stop) {
-                            float bmin;
-                            M.bmax = rr.mx;
-                            if (r3_bin_min(rr, M.fu, M.nfirst, bmin)) {
-                                M.bin_min = bmin;
-                                M.slope = (rr.mx - bmin) / (float)(bins - 1);
-                            } else {
-                                M.exact = 1;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-                STG_MARK(0);
-                if (M.stop) break;
-                if (M.exact) {   // rare: every workgroup scans the study itself
-                    float *s_cmax = reinterpret_cast<float *>(scr);
-                    const float m = exact_min_study(a, b, Ub, s_cmax, s_cmax + g.n, g, M);
-                    if (g.t == 0) {
-                        M.bin_min = m;
-                        M.slope = (M.bmax - m) / (float)(bins - 1);
-                    }
-                    __syncthreads();
-                }
-                const int itk = itn + 1;
-                const float bmin = M.bin_min, slope = M.slope;
-                const double rinv = 1.0 / (double)slope;
-                // ---- hist (S3): this workgroup's slice of compact U, then the grid's integer sums ----
-                for (int i = g.t; i < ST_HC * VH_MAX_BINS; i += g.n) Hc[i] = 0ull;
-                __syncthreads();
-                {
-                    unsigned long long *H = Hc + (lane & (ST_HC - 1)) * VH_MAX_BINS;
-                    const int64_t hchunk = ((n + G - 1) / G + 15) / 16 * 16;   // (16-aligned slices)
-                    const int64_t h0 = (int64_t)r * hchunk, h1 = min(n, h0 + hchunk);
-                    for (int64_t j0 = h0 + (int64_t)g.t * 16; j0 < h1; j0 += (int64_t)g.n * 16) {
-                        float u[16];
-                        if (j0 + 16 <= h1) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float4 v = reinterpret_cast<const float4 *>(Ub + j0)[q];
-                                u[4 * q] = v.x; u[4 * q + 1] = v.y; u[4 * q + 2] = v.z; u[4 * q + 3] = v.w;
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 16; ++k) u[k] = j0 + k < h1 ? Ub[j0 + k] : __int_as_float(0x7fc00000);
-                        }
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) {
-                            int idx;
-                            const unsigned long long w = hist_pack(u[k], bmin, rinv, bins, idx);
-                            atomicAdd(&H[idx], w);
-                        }
-                    }
-                }
-                __syncthreads();
-                for (int h = t; h < bins; h += ST_TPB) {
-                    unsigned long long cs = 0ull, os = 0ull;
-#pragma unroll
-                    for (int q = 0; q < ST_HC; ++q) {
-                        const unsigned long long w = Hc[q * VH_MAX_BINS + h];
-                        cs += hist_count(w);
-                        os += hist_osum(w);
-                    }
-                    if (cs) atomicAdd(HS + h, cs);
-                    if (os) atomicAdd(HS + VH_MAX_BINS + h, os);
-                }
-                STG_MARK(1);
-                grid.sync();
-                STG_MARK(8);
-                // the other parity's sums were last read by the previous iteration's E map
-                for (int e = r * ST_TPB + t; e < 2 * VH_MAX_BINS; e += G * ST_TPB) HSo[e] = 0ull;
-                // ---- emap (k_n4_study's arithmetic on the grid's sums) ----
-                {
-                    const int P = VH_FFT_P, off = (P - bins) / 2;
-                    const float sFWHM = a.fwhm / slope;
-                    const float ef = (float)(4.0 * LN2 / (double)(sFWHM * sFWHM));
-                    const float sf = (float)(2.0 * sqrt(LN2 / PI_D) / (double)sFWHM);
-                    const double2 twv = g.t < P / 2 ? a.tw[g.t] : make_double2(0.0, 0.0);
-                    for (int i = g.t; i < P; i += g.n) {
-                        const int h = i - off;
-                        unsigned long long s = 0ull;
-                        if (h >= 0 && h < bins) {
-                            s = (HS[h] << 24) - HS[VH_MAX_BINS + h];
-                            if (h > 0) s += HS[VH_MAX_BINS + h - 1];
-                        }
-                        V[fpad(i)] = make_double2((double)s * (1.0 / 16777216.0), 0.0);
-                        double fx;
-                        if (i == 0) {
-                            fx = (double)sf;
-                        } else if (i == P / 2) {
-                            fx = (double)sf * exp(-0.25 * (double)((float)P * (float)P) * (double)ef);
-                        } else {
-                            const float nf = (float)(i < P / 2 ? i : P - i);
-                            fx = (double)(sf * expf_cr_tail(-(nf * nf) * ef));
-                        }
-                        F[fpad(i)] = make_double2(fx, 0.0);
-                    }
-                    if (g.t < P / 2) TW[g.t] = twv;
-                    __syncthreads();
-                    if (g.w < 2) wave_fft_lds(g.w ? F : V, TW, false, FftId(), FftId());
-                    __syncthreads();
-                    for (int i = g.t; i < P; i += g.n) {
-                        const double2 f = F[fpad(i)], v = V[fpad(i)];
-                        const double fa = f.x, fb = f.y;
-                        const double gg = fa / ((fa * fa - (-fb) * fb) + (double)a.noise);
-                        V[fpad(i)] = make_double2(v.x * gg, v.y * gg);
-                    }
-                    __syncthreads();
-                    if (g.w == 0) wave_fft_lds(V, TW, true, FftId(), FftId());
-                    __syncthreads();
-                    for (int i = g.t; i < P; i += g.n) {
-                        const double ur = V[fpad(i)].x > 0.0 ? V[fpad(i)].x : 0.0;
-                        const float c = bmin + ((float)i - (float)off) * slope;
-                        DEN[fpad(i)] = make_double2(ur, 0.0);
-                        V[fpad(i)] = make_double2((double)c * ur, 0.0);
-                    }
-                    __syncthreads();
-                    if (g.w < 2) wave_fft_lds(g.w ? DEN : V, TW, false, FftId(), FftId());
-                    __syncthreads();
-                    for (int e = g.t; e < 2 * P; e += g.n) {
-                        double2 *const x = e < P ? V : DEN;
-                        const int i = e < P ? e : e - P;
-                        const double2 f = F[fpad(i)], v = x[fpad(i)];
-                        x[fpad(i)] = make_double2(v.x * f.x - v.y * f.y, v.x * f.y + v.y * f.x);
-                    }
-                    __syncthreads();
-                    if (g.w < 2) wave_fft_lds(g.w ? DEN : V, TW, true, FftId(), FftId());
-                    __syncthreads();
-                    for (int i = g.t; i < bins; i += g.n) {
-                        const double d = DEN[fpad(i + off)].x;
-                        sE[i] = d != 0.0 ? (float)(V[fpad(i + off)].x / d) : 0.0f;
-                    }
-                    __syncthreads();
-                }
-                STG_MARK(2);
-                // ---- fit: this workgroup's items into LDS, then into the grid's numerators ----
-                for (int e = g.t; e < 2 * nlat; e += g.n) numfix[e] = 0ull;
-                if (g.t == 0) M.item_ctr = 0;
-                __syncthreads();
-                for (;;) {
-                    const int item = next_item_g(M, ordr, a.nitems, r, G);
-                    if (item < 0) break;
-                    Item it;
-                    if (!study_item(it, a, b, item)) continue;
-                    fit_item<0, true>(it, T, Wk3, Wx3, ncy, ncz, a.Z, bins, Ub, n, sE, bmin, rinv, ring,
-                                      a.nb_ring, numfix);
-                }
-                __syncthreads();
-                for (int e = t; e < nlat; e += ST_TPB)
-                    fix128_flush(NS + 2 * e, NS + 2 * e + 1, numfix[2 * e], numfix[2 * e + 1]);
-                STG_MARK(3);
-                grid.sync();
-                STG_MARK(8);
-                // ---- lattice update and P1 (each workgroup its own copy, from the grid's sums) ----
-                for (int e = g.t; e < nlat; e += g.n) {
-                    const double d = fix128_get(NSd + 2 * e, NSd + 2 * e + 1);
-                    const double num = fix128_get(NS + 2 * e, NS + 2 * e + 1);
-                    const float phi = d != 0.0 ? (float)(num / d) : 0.0f;
-                    lat[e] += phi;
-                }
-                // the other parity's numerators were last read by the previous iteration's update
-                for (int e = r * ST_TPB + t; e < 2 * nlat; e += G * ST_TPB) NSo[e] = 0ull;
-                __syncthreads();
-                for (int e = g.t; e < ncx * ncy * a.Z; e += g.n) {
-                    const int ij = e / a.Z, z = e % a.Z;
-                    const float4 w = T.wz[z];
-                    const float *l = lat + ij * ncz + T.bz[z];
-                    P1[e] = (double)w.x * (double)l[0] + (double)w.y * (double)l[1] +
-                            (double)w.z * (double)l[2] + (double)w.w * (double)l[3];
-                }
-                if (g.t == 0) M.item_ctr = 0;
-                __syncthreads();
-                STG_MARK(4);
-                // ---- eval: this workgroup's items; U into the other buffer, d in raster order ----
-                const int uo = (uin + 1) % ST_NB;
-                {
-                    float *const Uo = a.U + uo * a.half + b * a.VS;
-                    float *const Dw = a.D + b * a.VS;
-                    float4 *const rp_out = rpart0 + uo * a.nitems;
-                    const bool first_of_level = itk == 1;
-                    const bool bo_mode = !(L == 0 && first_of_level);
-                    const bool same = !(first_of_level && L > 0);
-                    TabV To = T;
-                    int ncxo = ncx;
-                    if (!same) {
-                        const DevLevel &lo = a.lvs->lv[L - 1];
-                        To.wx = reinterpret_cast<const float4 *>(lo.ax[0].w);
-                        To.bx = lo.ax[0].base;
-                        ncxo = lo.ax[0].ncp;
-                    }
-                    float *const Tgn = Tg0 + (size_t)(tpar ^ 1) * a.tcap;
-                    const float *const Tgo = Tg0 + (size_t)tpar * a.tcap;
-                    for (;;) {
-                        const int item = next_item_g(M, ordr, a.nitems, r, G);
-                        if (item < 0) break;
-                        Item it;
-                        if (!study_item(it, a, b, item)) {
-                            if (lane == 0) {
-                                gd.ipart[2 * item] = 0.0;
-                                gd.ipart[2 * item + 1] = 0.0;
-                                rp_out[item] = make_float4(-FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX);
-                            }
-                            continue;
-                        }
-#define STG_EVAL(S, CM) eval_item<S, CM>(it, item, a.Z, a.CZ, T, To, ncx, ncy, ncxo, P1, Tgn, Tgo, bo_mode, \
-                                         Lb, Uo, Dw, n, gd.ipart, rp_out, pm)
-                        if (a.conv_mode == 0) {
-                            if (same) STG_EVAL(true, 0);
-                            else STG_EVAL(false, 0);
-                        } else {
-                            if (same) STG_EVAL(true, 1);
-                            else STG_EVAL(false, 1);
-                        }
-#undef STG_EVAL
-                    }
-                    __syncthreads();
-                    publish_range(gd, rpart0 + uo * a.nitems, ordr, a.nitems, uo, r, G);
-                }
-                STG_MARK(5);
-                grid.sync();
-                STG_MARK(8);
-                if (a.conv_mode == 0) {   // S7: the grid PC over every workgroup, d in raster order
-                    Pcg2Args A = gd.pc;
-                    A.skip_thresh = itk < a.lvs->max_iters[L] ? a.thresh : 0.0f;
-                    A.tag0 = (uint32_t)gi << 12;   // < 4096 scans per call (stage caps 40 + 40 + 48 rounds)
-                    const float *const Dr = a.D + b * a.VS;
-                    pcg2_body(A, PL, grid, [=](int64_t q) { return Dr[q]; });
-                    grid.sync();   // conv_w (one thread's store) to every workgroup
-                }
-                STG_MARK(6);
-                tpar ^= 1;
-                uin = uo;
-                itn = itk;
-                ++gi;
+        int itn = 0;
+        int uin = M.uin;
+        for (;;) {
+            float *const Ub = a.U + uin * a.half + b * a.VS;
+            const int p = gi & 1;
+            unsigned long long *const HS = gd.hsum + (size_t)p * 2 * VH_MAX_BINS;
+            unsigned long long *const HSo = gd.hsum + (size_t)(p ^ 1) * 2 * VH_MAX_BINS;
+            unsigned long long *const NS = gd.nsum + (size_t)p * 2 * a.lat_cap;
+            unsigned long long *const NSo = gd.nsum + (size_t)(p ^ 1) * 2 * a.lat_cap;
+            if (wv == 0) {   // ctrl (every workgroup, the same decision): the grid's records
+                double sd = 0.0, sd2 = 0.0;   // S7x of the last eval
+                if (a.conv_mode == 1 && itn > 0) s7x_sums(gd.ipart, a.nitems, sd, sd2);
+                ctrl_decide(a, M, r3_merge_records(gd.rrec + (size_t)uin * G, G), Ub, itn, L, [&] {
+                    return a.conv_mode == 1 ? conv_of(sd, sd2, (double)n) : (double)stb->conv_w;
+                });
             }
-            if (g.t == 0) {
-                M.itn = itn;
-                M.uin = uin;
+            __syncthreads();
+            STG_MARK(0);
+            if (M.stop) break;
+            if (M.exact) exact_bin_min(a, b, Ub, scr, M);   // rare: every workgroup scans the study itself
+            const int itk = itn + 1;
+            const float bmin = M.bin_min, slope = M.slope;
+            const double rinv = 1.0 / (double)slope;
+            // ---- hist (S3): this workgroup's slice of compact U, then the grid's integer sums ----
+            const int64_t hchunk = ((n + G - 1) / G + 15) / 16 * 16;   // (16-aligned slices)
+            hist_slice(Ub, (int64_t)r * hchunk, min(n, (int64_t)r * hchunk + hchunk), EW.Hc, bmin, rinv, a.bins);
+            for (int h = t; h < a.bins; h += ST_TPB) {
+                unsigned long long cs = 0ull, os = 0ull;
+#pragma unroll
+                for (int q = 0; q < ST_HC; ++q) {
+                    const unsigned long long w = EW.Hc[q * VH_MAX_BINS + h];
+                    cs += hist_count(w);
+                    os += hist_osum(w);
+                }
+                if (cs) atomicAdd(HS + h, cs);
+                if (os) atomicAdd(HS + VH_MAX_BINS + h, os);
             }
+            STG_MARK(1);
+            grid.sync();
+            STG_MARK(8);
+            // the other parity's sums were last read by the previous iteration's E map
+            for (int e = r * ST_TPB + t; e < 2 * VH_MAX_BINS; e += G * ST_TPB) HSo[e] = 0ull;
+            emap_phase(a, EW, sE, bmin, slope, [&](int h) {   // the grid's sums
+                unsigned long long s = (HS[h] << 24) - HS[VH_MAX_BINS + h];
+                if (h > 0) s += HS[VH_MAX_BINS + h - 1];
+                return s;
+            });
+            STG_MARK(2);
+            // ---- fit: this workgroup's items into LDS, then into the grid's numerators ----
+            fit_pass<0>(a, b, M, next, W, Ub, n, sE, bmin, rinv, ring, numfix);
+            for (int e = t; e < W.nlat; e += ST_TPB)
+                fix128_flush(NS + 2 * e, NS + 2 * e + 1, numfix[2 * e], numfix[2 * e + 1]);
+            STG_MARK(3);
+            grid.sync();
+            STG_MARK(8);
+            // ---- lattice update and P1 (each workgroup its own copy, from the grid's sums) ----
+            lattice_update(lat, W.nlat, [&](int e) { return fix128_get(NSd + 2 * e, NSd + 2 * e + 1); },
+                           [&](int e) { return fix128_get(NS + 2 * e, NS + 2 * e + 1); });
+            // the other parity's numerators were last read by the previous iteration's update
+            for (int e = r * ST_TPB + t; e < 2 * W.nlat; e += G * ST_TPB) NSo[e] = 0ull;
+            __syncthreads();
+            p1_from_lattice(lat, W.T, W.ncx * W.ncy, W.ncz, a.Z, P1);
+            if (t == 0) M.item_ctr = 0;
+            __syncthreads();
+            STG_MARK(4);
+            // ---- eval: this workgroup's items; U into the other buffer, d in raster order ----
+            const int uo = (uin + 1) % ST_NB;
+            eval_pass(a, b, next, W, L, itk, P1, tpar, Lb, a.U + uo * a.half + b * a.VS, n, gd.ipart,
+                      rpart0 + uo * a.nitems);
+            __syncthreads();
+            publish_range(gd, rpart0 + uo * a.nitems, ordr, a.nitems, uo, r, G);
+            STG_MARK(5);
+            grid.sync();
+            STG_MARK(8);
+            if (a.conv_mode == 0) {   // S7: the grid PC over every workgroup, d in raster order
+                Pcg2Args A = gd.pc;
+                A.skip_thresh = itk < a.lvs->max_iters[L] ? a.thresh : 0.0f;
+                A.tag0 = (uint32_t)gi << 12;   // < 4096 scans per call (stage caps 40 + 40 + 48 rounds)
+                const float *const Dr = a.D + b * a.VS;
+                pcg2_body(A, PL, grid, [=](int64_t q) { return Dr[q]; });
+                grid.sync();   // conv_w (one thread's store) to every workgroup
+            }
+            STG_MARK(6);
+            tpar ^= 1;
+            uin = uo;
+            itn = itk;
+            ++gi;
+        }
+        if (t == 0) {
+            M.itn = itn;
+            M.uin = uin;
         }
         __syncthreads();
         if (r == 0 && t == 0) {
             stb->iters_level[L] = M.itn;
             stb->conv_level[L] = (float)M.conv;
         }
-        if (L < a.nlev - 1) {   // exact subdivision of the lattice for the next level (every copy)
-            const int nl_max = lvl.ax[0].ncp * lvl.ax[1].ncp * lvl.ax[2].ncp;
-            float *T1 = reinterpret_cast<float *>(scr), *T2 = T1 + nl_max;
-            refine_axis_st(lat, T1, ncx, ncy, ncz, 0);
-            __syncthreads();
-            refine_axis_st(T1, T2, 2 * ncx - 3, ncy, ncz, 1);
-            __syncthreads();
-            refine_axis_st(T2, lat, 2 * ncx - 3, 2 * ncy - 3, ncz, 2);
-            __syncthreads();
-        }
+        if (L < a.nlev - 1)   // (every copy)
+            refine_lattice(lat, scr, W.ncx, W.ncy, W.ncz, lvl.ax[0].ncp * lvl.ax[1].ncp * lvl.ax[2].ncp);
     }
 #ifdef STG_PROF
     STG_MARK(7);
@@ -1662,15 +1399,8 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
                (unsigned long long)stg_p[6], (unsigned long long)stg_p[7], (unsigned long long)stg_p[8]);
 #endif
     if (r == 0) {   // final field's P1 for k_n4_final
-        const TabV T = tab_view(smem + a.o_tab, a.R, a.C, a.Z, a.kcap);
-        const int ncz = lvl.ax[2].ncp;
-        for (int e = t; e < p1last; e += ST_TPB) {
-            const int ij = e / a.Z, z = e % a.Z;
-            const float4 w = T.wz[z];
-            const float *l = lat + ij * ncz + T.bz[z];
-            a.P1out[b * a.q2cap + e] = (double)w.x * (double)l[0] + (double)w.y * (double)l[1] +
-                                       (double)w.z * (double)l[2] + (double)w.w * (double)l[3];
-        }
+        p1_from_lattice(lat, tab_view(smem + a.o_tab, a.R, a.C, a.Z, a.kcap), lvl.ax[0].ncp * lvl.ax[1].ncp,
+                        lvl.ax[2].ncp, a.Z, a.P1out + b * a.q2cap);
         if (t == 0) {
             stb->conv = M.conv;
             stb->active = 0;
@@ -1707,7 +1437,13 @@ __global__ void __launch_bounds__(1024) k_study_order(const VolScalars *sc, int6
 struct StudyLayout {
     size_t bytes;
     StudyArgs a;
+    bool grid;
 };
+
+// work items of a study: (64-column tile, 64-row slot) pairs
+static int study_nitems(const vh_batch *b) {
+    return (int)(b->n4_tiles * ((b->R + SLOT_R - 1) / SLOT_R));
+}
 
 // grid = true: the grid form's per-workgroup layout (k_n4_studyg): no item partials of the exact CoV
 // in LDS (they go to global memory), no PC area (the grid PC's LDS is static), the budget less that
@@ -1716,6 +1452,7 @@ static bool study_layout(const vh_batch *b, const vh_n4_params &prm, StudyLayout
                          int G = 1) {
     StudyArgs &a = out.a;
     std::memset(&a, 0, sizeof(a));
+    out.grid = grid;
     const int R = (int)b->R, C = (int)b->C, Z = (int)b->Z;
     int kcap = 0, nlat_max = 0, p1_max = 0, s_cap = 0;
     for (int L = 0; L < prm.n_levels; ++L) {
@@ -1756,7 +1493,7 @@ static bool study_layout(const vh_batch *b, const vh_n4_params &prm, StudyLayout
     a.o_tab = (int32_t)o; o += tb;
     a.o_lat = (int32_t)o; o += A(sizeof(float) * nlat_max);
     const int64_t nslots = (b->R + SLOT_R - 1) / SLOT_R;
-    const int64_t nitems = b->n4_tiles * nslots;
+    const int64_t nitems = study_nitems(b);
     a.o_ipart = (int32_t)o; o += grid ? 0 : A(sizeof(double) * 2 * (size_t)nitems);
     a.o_rpart = (int32_t)o; o += A(sizeof(float4) * ST_NB * (size_t)nitems);
     a.o_order = (int32_t)o; o += A(sizeof(int32_t) * (size_t)nitems);
@@ -1786,9 +1523,10 @@ bool vh_n4_study_eligible(const vh_batch *b, const vh_n4_params &prm, size_t *ld
     return ok;
 }
 
-void vh_launch_n4_study(vh_batch *b, const vh_n4_params &prm) {
-    StudyLayout Ly;
-    if (!study_layout(b, prm, Ly)) throw VhError{VH_ERR_ARG, "N4 study kernel: LDS budget exceeded"};
+// The launch arguments both kernels share: the layout's carve, the batch's buffers, the parameters,
+// and the device copy of the level tables (uploaded here, on the batch's stream).  vol0 = 0, no
+// study order, no PC drift buffer.
+static StudyArgs study_args(vh_batch *b, const vh_n4_params &prm, const StudyLayout &Ly) {
     StudyArgs a = Ly.a;
     a.I = b->d_hp;
     a.V = b->V;
@@ -1825,28 +1563,34 @@ void vh_launch_n4_study(vh_batch *b, const vh_n4_params &prm) {
     HIP_TRY(hipMemcpyAsync(b->d_study_lv, &h, sizeof(StudyLevels), hipMemcpyHostToDevice,
                            b->stream));
     a.lvs = (const StudyLevels *)b->d_study_lv;
+    // global state of the study: the fit denominators and the two T-window buffers (the sweep
+    // driver's d_den / d_T, vh_ensure_n4_workspace)
+    const int Lf = prm.n_levels - 1;
+    const int64_t cx = vh_level_ncp(prm, Lf, 0);
+    const int64_t nl = cx * vh_level_ncp(prm, Lf, 1) * vh_level_ncp(prm, Lf, 2);
+    if (!b->d_den || !b->d_T || b->lat_cap < nl || b->t_cap < cx * b->CZ)
+        throw VhError{VH_ERR_ARG, Ly.grid ? "N4 grid study kernel: workspace not prepared"
+                                          : "N4 study kernel: workspace not prepared"};
+    a.den = b->d_den;
+    a.lat_cap = b->lat_cap;
+    a.Tg = b->d_T;
+    a.tcap = b->t_cap;
     a.vol0 = 0;
     a.order = nullptr;
+    a.pcdrift = nullptr;
+    return a;
+}
+
+void vh_launch_n4_study(vh_batch *b, const vh_n4_params &prm) {
+    StudyLayout Ly;
+    if (!study_layout(b, prm, Ly)) throw VhError{VH_ERR_ARG, "N4 study kernel: LDS budget exceeded"};
+    StudyArgs a = study_args(b, prm, Ly);
     if (b->nb > 1 && b->nb <= 4096) {
         if (!b->d_study_order) HIP_TRY(hipMalloc(&b->d_study_order, sizeof(int32_t) * b->nb));
         k_study_order<<<1, 1024, 0, b->stream>>>(b->d_sc, b->nb, b->d_study_order);
         VH_CHECK_LAUNCH();
         a.order = b->d_study_order;
     }
-    // global state of the study: the fit denominators and the two T-window buffers (the sweep
-    // driver's d_den / d_T, vh_ensure_n4_workspace)
-    {
-        const int Lf = prm.n_levels - 1;
-        const int64_t cx = vh_level_ncp(prm, Lf, 0);
-        const int64_t nl = cx * vh_level_ncp(prm, Lf, 1) * vh_level_ncp(prm, Lf, 2);
-        if (!b->d_den || !b->d_T || b->lat_cap < nl || b->t_cap < cx * b->CZ)
-            throw VhError{VH_ERR_ARG, "N4 study kernel: workspace not prepared"};
-    }
-    a.den = b->d_den;
-    a.lat_cap = b->lat_cap;
-    a.Tg = b->d_T;
-    a.tcap = b->t_cap;
-    a.pcdrift = nullptr;
     if (PC_DRIFT) {
         if (!b->d_pcdrift) {
             HIP_TRY(hipMalloc(&b->d_pcdrift, sizeof(float) * ST_TPB * b->nb));
@@ -1893,69 +1637,17 @@ static int studyg_workgroups(const vh_batch *b, int nitems) {
 
 bool vh_n4_studyg_eligible(const vh_batch *b, const vh_n4_params &prm, size_t *lds_bytes) {
     if (b->n4_tiles == 0) return false;
-    StudyLayout L0;
-    study_layout(b, prm, L0);   // (item count)
-    const int G = studyg_workgroups(b, L0.a.nitems);
     StudyLayout L;
-    const bool ok = study_layout(b, prm, L, true, G);
+    const bool ok = study_layout(b, prm, L, true, studyg_workgroups(b, study_nitems(b)));
     if (lds_bytes) *lds_bytes = L.bytes;
     return ok;
 }
 
 void vh_launch_n4_studyg(vh_batch *b, const vh_n4_params &prm) {
-    StudyLayout L0;
-    study_layout(b, prm, L0);
-    const int G = studyg_workgroups(b, L0.a.nitems);
+    const int G = studyg_workgroups(b, study_nitems(b));
     StudyLayout Ly;
     if (!study_layout(b, prm, Ly, true, G)) throw VhError{VH_ERR_ARG, "N4 grid study kernel: LDS budget exceeded"};
-    StudyArgs a = Ly.a;
-    a.I = b->d_hp;
-    a.V = b->V;
-    a.L0 = b->d_L0;
-    a.U = b->d_U;
-    a.D = b->d_D;
-    a.half = b->nb * b->VS;
-    a.rs = b->d_rowstart;
-    a.rmask = b->d_rowmask;
-    a.rrs = b->d_rrank;
-    a.sc = b->d_sc;
-    a.st = b->d_st;
-    a.P1out = b->d_P1;
-    a.q2cap = b->q2_cap;
-    a.tw = b->d_twiddle;
-    a.VS = b->VS;
-    a.R = (int32_t)b->R;
-    a.C = (int32_t)b->C;
-    a.Z = (int32_t)b->Z;
-    a.CZ = (int32_t)b->CZ;
-    a.ntiles = (int32_t)b->n4_tiles;
-    a.nlev = prm.n_levels;
-    a.bins = prm.n_bins;
-    a.conv_mode = prm.conv_mode;
-    a.thresh = prm.conv_threshold;
-    a.fwhm = prm.fwhm;
-    a.noise = prm.wiener_noise;
-    StudyLevels h{};
-    for (int L = 0; L < prm.n_levels; ++L) {
-        h.max_iters[L] = prm.max_iters[L];
-        h.lv[L] = vh_dev_level(b, prm, L);
-    }
-    if (!b->d_study_lv) HIP_TRY(hipMalloc(&b->d_study_lv, sizeof(StudyLevels)));
-    HIP_TRY(hipMemcpyAsync(b->d_study_lv, &h, sizeof(StudyLevels), hipMemcpyHostToDevice, b->stream));
-    a.lvs = (const StudyLevels *)b->d_study_lv;
-    a.order = nullptr;
-    {
-        const int Lf = prm.n_levels - 1;
-        const int64_t cx = vh_level_ncp(prm, Lf, 0);
-        const int64_t nl = cx * vh_level_ncp(prm, Lf, 1) * vh_level_ncp(prm, Lf, 2);
-        if (!b->d_den || !b->d_T || b->lat_cap < nl || b->t_cap < cx * b->CZ)
-            throw VhError{VH_ERR_ARG, "N4 grid study kernel: workspace not prepared"};
-    }
-    a.den = b->d_den;
-    a.lat_cap = b->lat_cap;
-    a.Tg = b->d_T;
-    a.tcap = b->t_cap;
-    a.pcdrift = nullptr;
+    const StudyArgs a = study_args(b, prm, Ly);
     // per-launch global state: the sums of both parities and the denominators (zeroed here), the
     // range records, the exact-CoV item sums, the grid PC's records / ends / p values
     const int64_t NB = (int64_t)G * PC_TPB;
