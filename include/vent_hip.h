@@ -21,6 +21,9 @@
  *   vh_montage   Vent_Analysis.screenShot (montage array)     Vent_Analysis.py:458-520
  *   vh_recon     Vent_Analysis.process_RAW (k-space -> image) Vent_Analysis.py:537-540
  *   vh_batch_*   the same pipeline over a device-resident batch of studies (build-defined)
+ *   vh_batch_ci / vh_batch_set_defect / vh_batch_download_ci  calculate_CI of the batch's resident
+ *                defect maps (Vent_Analysis.py:265-271) with a per-study status and an int16 shell
+ *                map; a vh_ci_table may be destroyed as soon as vh_batch_ci has returned
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -148,7 +151,9 @@ int vh_ci(vh_ctx *ctx, const uint8_t *defect, int64_t R, int64_t C, int64_t Z, i
           int32_t *shell);
 /* The sphere table uploaded once for volumes of R rows and C columns (the px2vec stride of
  * CI.py:65-68): the same arrays as vh_ci; it stays in HBM until vh_ci_table_destroy.  vh_ci_tab is
- * vh_ci with such a table (ci_array and shell nullable): no per-call table work or upload. */
+ * vh_ci with such a table (ci_array and shell nullable): no per-call table work or upload.
+ * vh_ci_table_destroy waits for every user of the table first: the host-buffer calls of other
+ * threads, and the work vh_batch_ci enqueued with it on any batch's stream. */
 int vh_ci_table_create(vh_ctx *ctx, int64_t R, int64_t C, const int16_t *offs, const uint8_t *dup,
                        int64_t rows, const int32_t *bounds, const double *radii, int64_t nb,
                        vh_ci_table **out);
@@ -164,6 +169,18 @@ int vh_batch_run(vh_batch *b, const vh_run_opts *opts);      /* enqueue; returns
 int vh_batch_sync(vh_batch *b);
 int vh_batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *defect_border, uint8_t *lb,
                       vh_vdp_result *res /* [batch] */);
+/* CI of the batch's resident defect maps, enqueued on the batch's stream; returns before the GPU ends.
+ * The maps are the last vh_batch_run's or vh_batch_set_defect's; t is a table of the batch's context
+ * and (R, C) with at most 32767 shells.  Leaves the batch's maps and VDP results as they are.
+ * VH_CI_FORM (read at call time) picks the walk kernel: 0 / unset auto, 1 the one-study kernel of
+ * vh_ci over the batch, 2 the batch form. */
+int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox);
+/* Replace the resident defect maps (uint8 [nb][V], nonzero = defect): CI of edited or stored maps. */
+int vh_batch_set_defect(vh_batch *b, const uint8_t *defect);
+/* Waits for the stream.  ci_array f64 [nb][V] and shell int16 [nb][V] (the index into the table's
+ * radii, -1 off-defect) are nullable; ci_scalar[nb]; status[nb] is VH_OK, VH_ERR_EMPTY or
+ * VH_ERR_MAXRADIUS per study: such a study's scalar is 0.0 and the call still returns VH_OK. */
+int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *ci_scalar, int32_t *status);
 int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist /* [VH_COHORT_BINS] */);
 /* Kernel-class timing from HIP events on the context stream (opts.profile = 1).  name is one of
  * the classes listed by vh_batch_kernel_names (';'-separated). */

@@ -77,6 +77,9 @@ _SIGS = {
     "vh_batch_run": ([_P, ct.POINTER(RunOpts)], ct.c_int),
     "vh_batch_sync": ([_P], ct.c_int),
     "vh_batch_download": ([_P, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_ci": ([_P, _P, ct.c_double], ct.c_int),
+    "vh_batch_set_defect": ([_P, _P], ct.c_int),
+    "vh_batch_download_ci": ([_P, _P, _P, _P, _P], ct.c_int),
     "vh_batch_cohort_hist": ([_P, _P], ct.c_int),
     "vh_batch_kernel_names": ([], ct.c_char_p),
     "vh_batch_reset_timers": ([_P], ct.c_int),
@@ -424,6 +427,20 @@ def ci(defect, table, minvox, device=0, shell=True, out=None):
     return out, sc, sh
 
 
+def ci_expand(shell, radii, minvox):
+    """The float64 CI map of a shell map (Batch.download_ci(maps="shell")): radii[shell] * minvox on
+    the defect voxels (shell >= 0), 0.0 elsewhere -- the product CI.py:105 forms, so it equals the
+    device's float64 map bit for bit at a quarter of the transfer."""
+    sh = np.asarray(shell)
+    if not np.issubdtype(sh.dtype, np.integer):
+        raise ValueError(f"ci_expand: shell must be an integer array, got {sh.dtype}")
+    r = np.asarray(radii, dtype=np.float64)
+    if sh.size and int(sh.max()) >= r.shape[0]:
+        raise ValueError(f"ci_expand: shell {int(sh.max())} is past the table's {r.shape[0]} radii")
+    on = sh >= 0
+    return np.where(on, r[np.where(on, sh, 0)] * float(minvox), 0.0)
+
+
 def ctx_profile(on, device=0):
     """Time the kernel classes of the host-buffer entry points (vh_ci, ...) on this device's
     context (vh_ctx_profile); switching discards earlier timings."""
@@ -562,6 +579,48 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download(self.h, _ptr(out_n4), _ptr(d), _ptr(bo), _ptr(lb),
                                                 ct.cast(res, ct.c_void_p)), "vh_batch_download")
         return out_n4, d, bo, lb, list(res)
+
+    def upload_defect(self, d):
+        """Replace the resident defect maps (nonzero = defect): the CI of edited or stored maps."""
+        d = np.asarray(d)
+        if d.dtype != np.uint8:
+            d = d != 0
+        d = np.ascontiguousarray(d, dtype=np.uint8)
+        if d.shape != self.shape:
+            raise ValueError(f"batch expects {self.shape}")
+        self.ctx.check(self.L.vh_batch_set_defect(self.h, _ptr(d)), "vh_batch_set_defect")
+
+    def ci(self, vox, Rmax=50, table=None):
+        """Enqueue the cluster index of the resident defect maps (the last run's, or
+        upload_defect's) on the batch's stream; download_ci fetches it.  ``table``: a
+        sphere.SphereTable for this shape (default: compact_table_for(vox, Rmax, shape))."""
+        from .sphere import compact_table_for
+        _, R, C, Z = self.shape
+        if table is None:
+            table = compact_table_for(vox, Rmax, (R, C, Z))
+        minvox = float(np.min(vox))
+        with self.ctx.ci_lock:   # the handle is not evicted between the lookup and the enqueue
+            th = self.ctx.ci_table(table, R, C)
+            self.ctx.check(self.L.vh_batch_ci(self.h, th, ct.c_double(minvox)), "vh_batch_ci")
+        self.ci_radii = table.radii
+        self.ci_minvox = minvox
+
+    def download_ci(self, maps="shell"):
+        """(map, scalars, status) of the last ci(): the int16 shell map (``maps="shell"``: -1
+        off-defect, else the index into ``ci_radii``; ci_expand gives the float64 map), the float64
+        CI map (``"f64"``) or None; scalars float64 [B], NaN where status != 0; status int32 [B]:
+        VH_OK, VH_ERR_EMPTY (no defect voxels) or VH_ERR_MAXRADIUS per study."""
+        if maps not in ("shell", "f64", None):
+            raise ValueError('download_ci: maps is "shell", "f64" or None')
+        B = self.shape[0]
+        f64 = np.empty(self.shape, np.float64) if maps == "f64" else None
+        sh = np.empty(self.shape, np.int16) if maps == "shell" else None
+        sc = np.zeros(B, np.float64)
+        status = np.zeros(B, np.int32)
+        self.ctx.check(self.L.vh_batch_download_ci(self.h, _ptr(f64), _ptr(sh), _ptr(sc), _ptr(status)),
+                       "vh_batch_download_ci")
+        sc[status != VH_OK] = np.nan
+        return (f64 if maps == "f64" else sh), sc, status
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

@@ -157,6 +157,7 @@ static void batch_free(vh_batch *b) {
     dfree(b->d_bitmap); dfree(b->d_ci_list); dfree(b->d_ci_shell); dfree(b->d_ci_hist);
     dfree(b->d_ci_status);
     dfree(b->d_ci_count); dfree(b->d_ci_map);
+    dfree(b->d_ci_shell16); dfree(b->d_ci_next); dfree(b->d_ci_radii);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     if (b->st_n4) (void)hipStreamDestroy(b->st_n4);
     if (b->ev_n4_pre) (void)hipEventDestroy(b->ev_n4_pre);
@@ -676,15 +677,24 @@ int vh_ci_table_create(vh_ctx *ctx, int64_t R, int64_t C, const int16_t *offs, c
     })
 }
 
-// Tables are used only by ci_host on the context's scratch stream, under ctx->mu: taking the lock
-// waits for a CI call of another thread, and the scratch stream is drained before the hipFrees, so
-// no kernel can read a freed table (the destroy ran with neither).
+// Tables have two kinds of user.  ci_host (vh_ci, vh_ci_tab) runs on the context's scratch stream
+// under ctx->mu and synchronises before it returns: taking the lock waits for such a call of another
+// thread, and the scratch stream is drained before the hipFrees (the destroy ran with
+// neither).  vh_batch_ci only enqueues, on the batch's own stream, and returns: it records, still
+// under ctx->mu, an event on that stream after its last launch that reads the table (one event per
+// batch, vh_ci_table::users), and the destroy waits on every such event.  So no kernel can read a
+// freed table, and a table may be destroyed right after vh_batch_ci returns.
 int vh_ci_table_destroy(vh_ci_table *t) {
     if (!t) return VH_OK;
     vh_ctx *ctx = t->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     (void)hipSetDevice(ctx->device);
     if (ctx->scratch) (void)hipStreamSynchronize(ctx->scratch->stream);
+    for (auto &kv : t->users) {
+        (void)hipEventSynchronize(kv.second);
+        (void)hipEventDestroy(kv.second);
+    }
+    t->users.clear();
     vh_ci_table_free(t);
     return VH_OK;
 }
@@ -737,6 +747,73 @@ int vh_batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *defect_b
     })
 }
 
+// The CI of the resident defect maps (the last run's, or vh_batch_set_defect's): enqueue only.  The
+// table's radii are copied into the batch, so vh_batch_download_ci needs the table no more.
+int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox) {
+    if (!b || !t) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (t->ctx != b->ctx) throw VhError{VH_ERR_ARG, "sphere table of another context"};
+        if (!b->have_result && !b->have_defect)
+            throw VhError{VH_ERR_ARG, "no defect maps resident: vh_batch_run or vh_batch_set_defect first"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        std::lock_guard<std::mutex> lock(b->ctx->mu);   // against vh_ci_table_destroy of another thread
+        hipEvent_t &ev = t->users[b];
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        try {
+            vh_ci_run(b, t, minvox, nullptr, nullptr, vh_ci_batch_form(b));
+            if (t->nbs > b->ci_radii_cap) {
+                dfree(b->d_ci_radii);
+                b->ci_radii_cap = 0;
+                dalloc(&b->d_ci_radii, (size_t)t->nbs);
+                b->ci_radii_cap = t->nbs;
+            }
+            HIP_TRY(hipMemcpyAsync(b->d_ci_radii, t->d_radii, sizeof(double) * t->nbs, hipMemcpyDeviceToDevice,
+                                   b->stream));
+        } catch (...) {   // whatever was launched before the failure still reads the table
+            (void)hipEventRecord(ev, b->stream);
+            throw;
+        }
+        HIP_TRY(hipEventRecord(ev, b->stream));
+        b->ci_nbs = t->nbs;
+        b->ci_minvox = minvox;
+        b->have_ci = true;
+    })
+}
+
+int vh_batch_set_defect(vh_batch *b, const uint8_t *defect) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!defect) throw VhError{VH_ERR_ARG, "null defect maps"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        HIP_TRY(hipMemcpyAsync(b->d_defect, defect, (size_t)b->nb * b->V, hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        b->have_defect = true;
+    })
+}
+
+int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *ci_scalar, int32_t *status) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->have_ci) throw VhError{VH_ERR_ARG, "vh_batch_ci has not been called"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        const size_t NV = (size_t)b->nb * b->V;
+        if (ci_array) {
+            if (!b->d_ci_map) HIP_TRY(hipMalloc(&b->d_ci_map, sizeof(double) * NV));
+            vh_ci_expand(b, b->d_ci_map);
+            HIP_TRY(hipMemcpyAsync(ci_array, b->d_ci_map, sizeof(double) * NV, hipMemcpyDeviceToHost, b->stream));
+        }
+        if (shell)
+            HIP_TRY(hipMemcpyAsync(shell, b->d_ci_shell16, sizeof(int16_t) * NV, hipMemcpyDeviceToHost, b->stream));
+        std::vector<VolScalars> sc(b->nb);
+        d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);   // synchronises the stream
+        vh_ci_debug_check();
+        for (int64_t i = 0; i < b->nb; ++i) {
+            if (ci_scalar) ci_scalar[i] = sc[i].ci_scalar;
+            if (status) status[i] = sc[i].ci_status;
+        }
+    })
+}
+
 int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist) {
     API_TRY(b->ctx, {
         HIP_TRY(hipStreamSynchronize(b->stream));
@@ -746,7 +823,7 @@ int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist) {
 
 const char *vh_batch_kernel_names(void) {
     return "mask_stats;gather;sort;mean;classify;cohort;kmeans;snr;border;n4_init;n4_den;n4_hist;"
-           "n4_fit;n4_contract;n4_eval;n4_welford;n4_pcw;n4_pcg;n4_final;n4_study;ci_walk;vdp_chain";
+           "n4_fit;n4_contract;n4_eval;n4_welford;n4_pcw;n4_pcg;n4_final;n4_study;ci_walk;vdp_chain;ci_walk_b";
 }
 
 int vh_batch_reset_timers(vh_batch *b) {

@@ -267,7 +267,16 @@ struct vh_batch {
     int64_t ci_nb_cap = 0;
     int32_t *d_ci_status = nullptr;  // [nb]
     unsigned long long *d_ci_count = nullptr;   // [nb]
-    double *d_ci_map = nullptr;      // [nb][V] float64 CI map (vh_ci)
+    double *d_ci_map = nullptr;      // [nb][V] float64 CI map (vh_ci, vh_batch_download_ci)
+    // vh_batch_ci (the CI of the resident defect maps)
+    int16_t *d_ci_shell16 = nullptr; // [nb][V] shell of each defect voxel, -1 elsewhere
+    uint32_t *d_ci_next = nullptr;   // [nb][64] (one per 256 bytes) next unclaimed slot of the study's defect list (k_ci_walk_b)
+    double *d_ci_radii = nullptr;    // [ci_nbs] the last table's radii: the batch's own copy, so the
+    int64_t ci_radii_cap = 0;        //   float64 map can be expanded after the table is destroyed
+    int64_t ci_nbs = 0;
+    double ci_minvox = 0.0;
+    bool have_defect = false;        // vh_batch_set_defect uploaded the defect maps
+    bool have_ci = false;            // vh_batch_ci has been enqueued
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -290,6 +299,9 @@ struct vh_ci_table {
     int32_t *d_offL = nullptr;       // [rows] px2vec offsets, CI_SENTINEL for duplicate rows
     int32_t *d_bounds = nullptr;     // [nbs] shell prefix lengths
     double *d_radii = nullptr;       // [nbs] r[b - 1]
+    // vh_batch_ci: one event per batch that used the table, recorded on that batch's stream after
+    // its CI launches (under ctx->mu); vh_ci_table_destroy waits on all of them before the frees
+    mutable std::map<const vh_batch *, hipEvent_t> users;
 };
 
 // ---- timing helper ----------------------------------------------------------------------------
@@ -328,7 +340,12 @@ void vh_n4_prepare_tables(vh_batch *b, const vh_n4_params &prm);
 vh_ci_table *vh_ci_table_build(vh_ctx *ctx, int64_t R, int64_t C, const int16_t *offs, const uint8_t *dup,
                                int64_t rows, const int32_t *bounds, const double *radii, int64_t nbs);
 void vh_ci_table_free(vh_ci_table *t);
-void vh_ci_run(vh_batch *b, const vh_ci_table *t, double minvox, double *d_ci, VolScalars *h_sc = nullptr);
+// form 0: the host-buffer calls (k_ci_walk, int32 shells); 1 / 2: vh_batch_ci with k_ci_walk /
+// k_ci_walk_b, shells as int16 in d_ci_shell16
+void vh_ci_run(vh_batch *b, const vh_ci_table *t, double minvox, double *d_ci, VolScalars *h_sc = nullptr,
+               int form = 0);
+int vh_ci_batch_form(const vh_batch *b);   // VH_CI_FORM, read at call time: 1 or 2
+void vh_ci_expand(vh_batch *b, double *d_ci);   // d_ci_shell16 -> the float64 map, on the batch's stream
 void vh_ci_debug_check();   // VH_DEBUG_BOUNDS builds: raise the CI kernels' first bounds violation
 void vh_ensure_n4_workspace(vh_batch *b, const vh_n4_params &prm);
 
