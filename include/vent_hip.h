@@ -24,6 +24,10 @@
  *   vh_batch_ci / vh_batch_set_defect / vh_batch_download_ci  calculate_CI of the batch's resident
  *                defect maps (Vent_Analysis.py:265-271) with a per-study status and an int16 shell
  *                map; a vh_ci_table may be destroyed as soon as vh_batch_ci has returned
+ *   vh_batch_select_defect / vh_batch_download_defect / vh_batch_km_cuts / vh_defect_map  the defect
+ *                map, border and count of the linear-binning or k-means VDP (or the mean-anchored
+ *                one again), and the k-means label map, so calculate_CI / exportDICOM / screenShot
+ *                can show the defect any of calculate_VDP's three percentages counts (build-defined)
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -141,6 +145,12 @@ int vh_snr(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R, int64_t
 int vh_vdp(vh_ctx *ctx, const float *hp, const float *n4, const uint8_t *mask, int64_t R,
            int64_t C, int64_t Z, int64_t batch, float thresh, const double vox[3],
            uint8_t *defect, uint8_t *defect_border, uint8_t *lb, vh_vdp_result *res);
+/* Host-buffer form of vh_batch_select_defect / vh_batch_download_defect (declared below) for one
+ * call: the post-N4 chain (no N4, no SNR) on the scratch batch, then the selection.  Outputs
+ * nullable; VH_ERR_EMPTY for an empty-mask study, like vh_vdp. */
+int vh_defect_map(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                  int64_t batch, float thresh, int source, int medfilt,
+                  uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count);
 /* Cluster index map.  The sphere table comes from the host (reference-identical rows; see
  * vent_analysis_amd/sphere.py): offs int16 [rows][3] (dx,dy,dz), dup uint8 [rows], bounds int32
  * [nb] prefix lengths, radii float64 [nb] (= r[b-1]).  Outputs: ci_array float64 volume,
@@ -181,6 +191,30 @@ int vh_batch_set_defect(vh_batch *b, const uint8_t *defect);
  * radii, -1 off-defect) are nullable; ci_scalar[nb]; status[nb] is VH_OK, VH_ERR_EMPTY or
  * VH_ERR_MAXRADIUS per study: such a study's scalar is 0.0 and the call still returns VH_OK. */
 int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *ci_scalar, int32_t *status);
+/* The defect map of any of the three thresholdings calculate_VDP reports, built on the device from
+ * the last vh_batch_run's N4 and scalars.  Each source has a raw map: MEAN float32(N4 / mean_anchor)
+ * < thresh (the run's thresh), LB the voxels of linear-binning class 1 or 2, KM the voxels of the
+ * lowest non-empty k-means cluster; all inside mask != 0.  medfilt 0 keeps the raw map (2-D border),
+ * 1 applies the reference's per-slice 3x3 zero-padded median (2-D border), 2 the build-defined
+ * 3x3x3 majority (3-D border), as vh_run_opts.morph3d does.  MEAN with medfilt 1 (2 after a morph3d
+ * run) reproduces the run's own defect / defect_border byte for byte. */
+#define VH_DEFECT_MEAN 0
+#define VH_DEFECT_LB   1
+#define VH_DEFECT_KM   2
+/* Rebuild the resident defect map and border from the last vh_batch_run's N4 and scalars (enqueue
+ * only).  Replaces what vh_batch_run / vh_batch_set_defect left in them; vh_batch_ci, vh_batch_download
+ * then see the selected map.  The run's vh_vdp_result values are left as they are.  VH_ERR_ARG,
+ * with nothing enqueued: source or medfilt out of range, no vh_batch_run yet, KM after a run with
+ * do_kmeans = 0, a shape the plane sweep does not take (more than 816 slices). */
+int vh_batch_select_defect(vh_batch *b, int source, int medfilt);
+/* Waits for the stream.  All nullable: defect / border / km uint8 [nb][V]; count int64 [nb] (voxels
+ * of the selected map; the run's own defect count when no selection followed it); km is computed on
+ * demand (needs do_kmeans): 0 off-mask, else 1 + the voxel's cluster in k-means' final partition
+ * (an empty cluster's index is skipped: two distinct values give labels 1 and 4). */
+int vh_batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count);
+/* The three k-means cut values per study: the smallest value of clusters 1..3, +inf where the cut
+ * is at n; float [nb][3].  (For a histogram display with the cluster edges.) */
+int vh_batch_km_cuts(vh_batch *b, float *cuts);
 int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist /* [VH_COHORT_BINS] */);
 /* Kernel-class timing from HIP events on the context stream (opts.profile = 1).  name is one of
  * the classes listed by vh_batch_kernel_names (';'-separated). */

@@ -228,6 +228,28 @@ class Vent_Analysis:
         self.n4_iterations = list(r.n4_iters)[:4]
         print('\033[32mcalculate_VDP ran successfully\033[37m')
 
+    def select_defect(self, method='mean', medfilt=1, thresh=0.6):
+        """Make ``defectArray`` / ``defectBorder`` the defect map of one of calculate_VDP's three
+        thresholdings (build-defined; the reference keeps a map of the mean-anchored one only):
+        ``method`` 'mean' (N4 / mean < thresh), 'lb' (linear-binning classes 1 and 2) or 'kmeans' (the
+        lowest k-means cluster); ``medfilt`` 0 the raw map, 1 the reference's per-slice 3x3 median,
+        2 the 3x3x3 majority with the 3-D border.  Needs N4HPvent (calculate_VDP first).  The maps
+        are scaled by the mask value as calculate_VDP scales them; calculate_CI, exportDICOM,
+        screenShot and build4DdataArray then work on the chosen map.  Returns the map's percentage of
+        the mask, 100 * count / sum(mask) for a 0/1 mask; metadata and defectArrayLB are left alone."""
+        if isinstance(self.N4HPvent, str):
+            raise ValueError("select_defect: N4HPvent is not set (run calculate_VDP first)")
+        mask_u8, v = _mask_value(self.mask)
+        d, bo, cnt = _lib.defect_map(np.asarray(self.N4HPvent), mask_u8, method, medfilt=medfilt,
+                                     thresh=thresh, device=self.device)
+        msum = np.sum(self.mask)
+        self.defectBorder = bo[0] == 1
+        if v == 1:
+            self.defectArray = d[0].astype(np.float64)
+            return 100 * np.float64(cnt[0]) / msum
+        self.defectArray = d[0].astype(np.float64) * v
+        return 100 * np.sum(self.defectArray) / msum
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

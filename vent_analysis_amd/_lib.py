@@ -21,6 +21,19 @@ VH_OK, VH_ERR_ARG, VH_ERR_HIP, VH_ERR_NOMEM, VH_ERR_MAXRADIUS, VH_ERR_EMPTY, VH_
     VH_ERR_NODEV, VH_ERR_INDEX = range(9)
 COHORT_BINS = 1024
 COMM_ID_BYTES = 128
+VH_DEFECT_MEAN, VH_DEFECT_LB, VH_DEFECT_KM = range(3)   # vh_batch_select_defect sources
+_DEFECT_SOURCES = {"mean": VH_DEFECT_MEAN, "lb": VH_DEFECT_LB, "kmeans": VH_DEFECT_KM}
+
+
+def defect_source(source) -> int:
+    """'mean' | 'lb' | 'kmeans' or the VH_DEFECT_* ints -> the int; anything else raises ValueError."""
+    if isinstance(source, str):
+        if source not in _DEFECT_SOURCES:
+            raise ValueError(f"defect source is 'mean', 'lb' or 'kmeans', got {source!r}")
+        return _DEFECT_SOURCES[source]
+    if isinstance(source, (bool, float)) or int(source) != source:
+        raise ValueError(f"defect source is 'mean', 'lb' or 'kmeans' or 0..2, got {source!r}")
+    return int(source)   # (the library checks the range)
 
 
 class N4Params(ct.Structure):
@@ -80,6 +93,11 @@ _SIGS = {
     "vh_batch_ci": ([_P, _P, ct.c_double], ct.c_int),
     "vh_batch_set_defect": ([_P, _P], ct.c_int),
     "vh_batch_download_ci": ([_P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_select_defect": ([_P, ct.c_int, ct.c_int], ct.c_int),
+    "vh_batch_download_defect": ([_P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_km_cuts": ([_P, _P], ct.c_int),
+    "vh_defect_map": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_float, ct.c_int, ct.c_int, _P, _P, _P,
+                       _P], ct.c_int),
     "vh_batch_cohort_hist": ([_P, _P], ct.c_int),
     "vh_batch_kernel_names": ([], ct.c_char_p),
     "vh_batch_reset_timers": ([_P], ct.c_int),
@@ -401,6 +419,26 @@ def vdp(n4v, mask, vox, hp=None, thresh=0.6, device=0):
     return defect, bord, lb, list(res)
 
 
+def defect_map(n4, mask, source, medfilt=1, thresh=0.6, device=0, km=False):
+    """The defect map of one thresholding from host arrays (vh_defect_map): ``source`` 'mean' | 'lb'
+    | 'kmeans', ``medfilt`` 0 / 1 / 2 as Batch.select_defect.  Returns (defect, border, count), uint8
+    [B][R][C][Z] twice and int64 [B], with the k-means label map appended when ``km``."""
+    c = context(device)
+    n = as_batch(n4, np.float32)
+    m = as_batch(mask, np.uint8)
+    if n.shape != m.shape:
+        raise ValueError("N4 and mask shapes differ")
+    B, R, C, Z = n.shape
+    d = np.empty((B, R, C, Z), np.uint8)
+    bo = np.empty_like(d)
+    lab = np.empty_like(d) if km else None
+    cnt = np.zeros(B, np.int64)
+    c.check(c.L.vh_defect_map(c.h, _ptr(n), _ptr(m), R, C, Z, B, ct.c_float(thresh),
+                              defect_source(source), int(medfilt), _ptr(d), _ptr(bo), _ptr(lab),
+                              _ptr(cnt)), "vh_defect_map")
+    return (d, bo, cnt, lab) if km else (d, bo, cnt)
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -589,6 +627,32 @@ class Batch:
         if d.shape != self.shape:
             raise ValueError(f"batch expects {self.shape}")
         self.ctx.check(self.L.vh_batch_set_defect(self.h, _ptr(d)), "vh_batch_set_defect")
+
+    def select_defect(self, source, medfilt=1):
+        """Rebuild the resident defect map and border from the last run's N4 and scalars (enqueue
+        only): ``source`` 'mean' | 'lb' | 'kmeans' (or VH_DEFECT_*), ``medfilt`` 0 raw, 1 the per-slice
+        3x3 median, 2 the 3x3x3 majority with the 3-D border.  ci(), download() and download_defect()
+        then see the selected map; the run's results stay as they are."""
+        self.ctx.check(self.L.vh_batch_select_defect(self.h, defect_source(source), int(medfilt)),
+                       "vh_batch_select_defect")
+
+    def download_defect(self, km=False):
+        """(defect, border, count) of the resident maps -- uint8 [B][R][C][Z] twice and int64 [B] --
+        plus the k-means label map (0 off-mask, else 1 + cluster) when ``km``."""
+        d = np.empty(self.shape, np.uint8)
+        bo = np.empty(self.shape, np.uint8)
+        lab = np.empty(self.shape, np.uint8) if km else None
+        cnt = np.zeros(self.shape[0], np.int64)
+        self.ctx.check(self.L.vh_batch_download_defect(self.h, _ptr(d), _ptr(bo), _ptr(lab), _ptr(cnt)),
+                       "vh_batch_download_defect")
+        return (d, bo, cnt, lab) if km else (d, bo, cnt)
+
+    def km_cuts(self):
+        """float32 [B][3]: the smallest value of k-means clusters 1..3 of each study, +inf where
+        the cut is at n (the cluster and all above it are empty)."""
+        cuts = np.zeros((self.shape[0], 3), np.float32)
+        self.ctx.check(self.L.vh_batch_km_cuts(self.h, _ptr(cuts)), "vh_batch_km_cuts")
+        return cuts
 
     def ci(self, vox, Rmax=50, table=None):
         """Enqueue the cluster index of the resident defect maps (the last run's, or

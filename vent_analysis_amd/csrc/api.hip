@@ -10,6 +10,7 @@
 #include <memory>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 
 #ifndef VH_COPY_THREADS
@@ -146,7 +147,7 @@ static void batch_free(vh_batch *b) {
     clear_timers(b);
     dfree(b->d_kst);
     dfree(b->d_hp); dfree(b->d_mask); dfree(b->d_n4);
-    dfree(b->d_defect); dfree(b->d_border); dfree(b->d_lb);
+    dfree(b->d_defect); dfree(b->d_border); dfree(b->d_lb); dfree(b->d_km);
     dfree(b->d_colrange); dfree(b->d_colcount); dfree(b->d_colstart); dfree(b->d_colbits); dfree(b->d_colbnz); dfree(b->d_snrpart);
     dfree(b->d_rowany); dfree(b->d_colany); dfree(b->d_sliceany);
     dfree(b->d_sc); dfree(b->d_part); dfree(b->d_keys0); dfree(b->d_keys1); dfree(b->d_tilecnt);
@@ -290,6 +291,9 @@ static void batch_run(vh_batch *b, const vh_run_opts &o, int n4_src) {
     }
     vh_launch_vdp_chain(b, n4, o);
     b->have_result = true;
+    b->d_n4_last = n4;
+    b->km_valid = false;
+    b->sel_valid = false;
 }
 
 // the study kernel's spin-wait watchdog (n4_study.hip st_spin) leaves N4State.active = -2
@@ -788,6 +792,115 @@ int vh_batch_set_defect(vh_batch *b, const uint8_t *defect) {
         HIP_TRY(hipMemcpyAsync(b->d_defect, defect, (size_t)b->nb * b->V, hipMemcpyHostToDevice, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         b->have_defect = true;
+        b->sel_valid = false;
+    })
+}
+
+// the argument checks of the selection calls (host only: nothing is enqueued before they pass)
+static void check_select(const vh_batch *b, int source, int medfilt) {
+    if (source < VH_DEFECT_MEAN || source > VH_DEFECT_KM)
+        throw VhError{VH_ERR_ARG, "source must be VH_DEFECT_MEAN, _LB or _KM"};
+    if (medfilt < 0 || medfilt > 2) throw VhError{VH_ERR_ARG, "medfilt must be 0, 1 or 2"};
+    if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    if (source == VH_DEFECT_KM && !b->opts.do_kmeans)
+        throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
+}
+
+static void batch_select(vh_batch *b, int source, int medfilt) {
+    // the label map rides along once a caller has asked for it (d_km exists) and the run has cuts
+    uint8_t *km = b->opts.do_kmeans ? b->d_km : nullptr;
+    if (!vh_launch_defect_select(b, b->d_n4_last, b->opts.thresh, source, medfilt, km))
+        throw VhError{VH_ERR_ARG, "vh_batch_select_defect: this shape has no plane-sweep geometry"};
+    if (km) b->km_valid = true;
+    b->sel_valid = true;
+}
+
+static void batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count) {
+    const size_t NV = (size_t)b->nb * b->V;
+    hipStream_t st = b->stream;
+    if (km && !b->km_valid) {
+        if (!b->d_km) dalloc(&b->d_km, NV);
+        vh_launch_km_labels(b, b->d_n4_last, b->d_km);
+        b->km_valid = true;
+    }
+    if (defect) HIP_TRY(hipMemcpyAsync(defect, b->d_defect, NV, hipMemcpyDeviceToHost, st));
+    if (border) HIP_TRY(hipMemcpyAsync(border, b->d_border, NV, hipMemcpyDeviceToHost, st));
+    if (km) HIP_TRY(hipMemcpyAsync(km, b->d_km, NV, hipMemcpyDeviceToHost, st));
+    std::vector<VolScalars> sc(b->nb);
+    d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);   // synchronises the stream
+    if (count)
+        for (int64_t i = 0; i < b->nb; ++i) count[i] = b->sel_valid ? sc[i].n_sel : sc[i].n_defect;
+}
+
+int vh_batch_select_defect(vh_batch *b, int source, int medfilt) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        check_select(b, source, medfilt);
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_select(b, source, medfilt);
+    })
+}
+
+int vh_batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+        if (km && !b->opts.do_kmeans)
+            throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_download_defect(b, defect, border, km, count);
+    })
+}
+
+int vh_batch_km_cuts(vh_batch *b, float *cuts) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!cuts) throw VhError{VH_ERR_ARG, "null cuts"};
+        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+        if (!b->opts.do_kmeans)
+            throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        std::vector<VolScalars> sc(b->nb);
+        d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);
+        for (int64_t i = 0; i < b->nb; ++i)
+            for (int j = 0; j < 3; ++j) {
+                // (an empty study has no cuts: km_valid is 0 from the run's initialisation)
+                const uint32_t k = sc[i].km_cut[j];
+                const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;   // key2f on the host
+                float f = std::numeric_limits<float>::infinity();
+                if (sc[i].n_mask > 0 && ((sc[i].km_valid >> j) & 1)) memcpy(&f, &u, sizeof f);
+                cuts[i * 3 + j] = f;
+            }
+    })
+}
+
+int vh_defect_map(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                  int64_t batch, float thresh, int source, int medfilt, uint8_t *defect, uint8_t *border,
+                  uint8_t *km, int64_t *count) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!n4 || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        if (source < VH_DEFECT_MEAN || source > VH_DEFECT_KM || medfilt < 0 || medfilt > 2)
+            throw VhError{VH_ERR_ARG, "source must be VH_DEFECT_MEAN, _LB or _KM and medfilt 0, 1 or 2"};
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        const size_t NV = (size_t)batch * b->V;
+        HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
+        batch_upload(b, nullptr, mask);
+        vh_run_opts o;
+        vh_default_run_opts(&o);
+        o.do_n4 = 0;
+        o.do_snr = 0;
+        o.do_kmeans = source == VH_DEFECT_KM || km != nullptr;
+        o.thresh = thresh;
+        o.profile = ctx->profile;
+        batch_run(b, o, 2);
+        batch_select(b, source, medfilt);
+        batch_download_defect(b, defect, border, km, count);
+        std::vector<VolScalars> sc(batch);
+        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < batch; ++i)
+            if (sc[i].n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
     })
 }
 
@@ -823,7 +936,7 @@ int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist) {
 
 const char *vh_batch_kernel_names(void) {
     return "mask_stats;gather;sort;mean;classify;cohort;kmeans;snr;border;n4_init;n4_den;n4_hist;"
-           "n4_fit;n4_contract;n4_eval;n4_welford;n4_pcw;n4_pcg;n4_final;n4_study;ci_walk;vdp_chain;ci_walk_b";
+           "n4_fit;n4_contract;n4_eval;n4_welford;n4_pcw;n4_pcg;n4_final;n4_study;ci_walk;vdp_chain;ci_walk_b;defect_sel";
 }
 
 int vh_batch_reset_timers(vh_batch *b) {

@@ -1108,7 +1108,17 @@ struct PsGeom {
     int XS, TY, nxs, nyt;
 };
 
-enum { PS_CL2 = 0, PS_CL3 = 1, PS_BORDER = 2 };
+// PS_SEL + 3 * medfilt + source: the defect selection (vh_batch_select_defect).  The raw ring
+// takes the source's test (VH_DEFECT_MEAN / _LB / _KM) instead of the classify threshold and no LB
+// classes are written; medfilt 0 passes raw through (no median, 2-D border), 1 is CL2's median and
+// border, 2 CL3's.  The lb argument then takes the k-means label map (or null).
+enum { PS_CL2 = 0, PS_CL3 = 1, PS_BORDER = 2, PS_SEL = 3 };
+
+// k-means label of a masked value from the three cut keys: 1 + #{valid cuts j : key >= cut j}
+__device__ __forceinline__ uint32_t km_label(uint32_t key, const uint32_t (&ck)[3], const uint32_t (&cv)[3]) {
+    return 1u + ((uint32_t)(key >= ck[0]) & cv[0]) + ((uint32_t)(key >= ck[1]) & cv[1]) +
+           ((uint32_t)(key >= ck[2]) & cv[2]);
+}
 
 // byte lanes >= k (bias = 128 - k, added to every byte lane): 1, else 0
 __device__ __forceinline__ uint32_t ps_atleast(uint32_t s, uint32_t bias) {
@@ -1153,6 +1163,9 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
                                                  PsGeom g, uint8_t *defect, uint8_t *border,
                                                  uint8_t *lb, unsigned long long *cnt_out) {
     constexpr bool CL = MODE != PS_BORDER;
+    constexpr bool SEL = MODE >= PS_SEL;
+    constexpr int SRC = SEL ? (MODE - PS_SEL) % 3 : -1, MF = SEL ? (MODE - PS_SEL) / 3 : -1;
+    constexpr bool M3 = MODE == PS_CL3 || MF == 2;   // 3x3x3 median, 3-D border
     extern __shared__ uint32_t ps_lds[];
     const int64_t b = blockIdx.y;
     const int xs = (int)(blockIdx.x % (unsigned)g.nxs), yt = (int)(blockIdx.x / (unsigned)g.nxs);
@@ -1176,6 +1189,21 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
         f_thr = le_bound(tpred, m);
         const float edges[5] = {0.16f, 0.34f, 0.52f, 0.7f, 0.88f};
         for (int e = 0; e < 5; ++e) f_lb[e] = le_bound(edges[e], p99);
+    }
+    // PS_SEL: MEAN tests classify's bound of the threshold, LB its bound of edge 0.34 (classes 1
+    // and 2: the bounds are monotone in the edge), both with the same IEEE-division fallback; KM
+    // compares the voxel's k-means label with the lowest non-empty cluster's.  An empty study's
+    // cuts are undefined (k-means returned early) and never read: its mask bytes are all 0, so
+    // every output is 0.
+    uint32_t ck[3] = {0u, 0u, 0u}, cv[3] = {0u, 0u, 0u}, klow = 0u;
+    bool labels = false;
+    if constexpr (SEL) {
+        labels = (SRC == VH_DEFECT_KM || lb != nullptr) && sc[b].n_mask > 0;
+        if (labels) {
+            const int valid = sc[b].km_valid;
+            for (int j = 0; j < 3; ++j) { ck[j] = sc[b].km_cut[j]; cv[j] = (uint32_t)(valid >> j) & 1u; }
+            klow = 1u + (uint32_t)sc[b].km_low;
+        }
     }
 
     // word sets: loads (raw rows, or def rows in border mode), def rows, output rows
@@ -1288,7 +1316,14 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
                     for (int q = 0; q < 4; ++q) {   // branch-free: deselected bytes give 0
                         const bool on = ((mk[k] >> (8 * q)) & 0xFFu) != 0u;
                         uint32_t below, cls;
-                        if (fast) {
+                        if constexpr (SEL) {
+                            // cls: the k-means label (compared in the sort's key domain)
+                            cls = labels ? km_label(f2key(v[q]), ck, cv) : 0u;
+                            if (SRC == VH_DEFECT_KM) below = cls == klow;
+                            else if (SRC == VH_DEFECT_LB)
+                                below = fast ? v[q] < f_lb[1] : (uint32_t)(lb_class(v[q] / p99) - 1) < 2u;
+                            else below = fast ? v[q] < f_thr : (v[q] / m) < thresh;
+                        } else if (fast) {
                             below = v[q] < f_thr;
                             // LB class = 6 - #(edges with RN(v / p99) <= edge); NaN -> 0
                             const uint32_t nle = (uint32_t)(v[q] < f_lb[0]) + (uint32_t)(v[q] < f_lb[1]) +
@@ -1304,10 +1339,10 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
                         cls = (on && lbk) ? cls : 0u;
                         r |= below << (8 * q);
                         c |= cls << (8 * q);
-                        n_lb12 += (cls == 1u || cls == 2u);
+                        if constexpr (!SEL) n_lb12 += (cls == 1u || cls == 2u);
                     }
                     raw[(p & 3) * RW + l_lds[k]] = r;
-                    if (lbk)
+                    if (lbk && (!SEL || lb))   // (selection: the label map, when asked for)
                         store_word(lb, vb + (int64_t)p * g.CZ + l_goff[k], c, l_f[k]);
                 }
             }
@@ -1325,9 +1360,13 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
                                ((r1[j] + r1[j + ZW]) + r1[j + 2 * ZW]) +
                                ((r2[j] + r2[j + ZW]) + r2[j + 2 * ZW]);
                     };
+                    if constexpr (MF == 0) {   // no median: the raw word of (xd, y)
+                        def[(xd & 3) * DW + i] = r1[i + ZW];
+                        continue;
+                    }
                     const uint32_t s0 = sum9(i);
                     uint32_t d;
-                    if (MODE == PS_CL3) {
+                    if (M3) {
                         const uint32_t sm = (d_f[k] & PSF_ZW0) ? 0u : sum9(i - 1);
                         const uint32_t sp = (d_f[k] & PSF_ZWL) ? 0u : sum9(i + 1);
                         const uint32_t s = s0 + ((s0 << 8) | (sm >> 24)) + ((s0 >> 8) | (sp << 24));
@@ -1360,7 +1399,7 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
                 const uint32_t ay = (!(f & PSF_Y0) && (f & PSF_YL)) ? D : d0[i + ZW];
                 const uint32_t by = (f & PSF_Y0) ? D : d0[i - ZW];
                 uint32_t gr = (ax ^ bx) | (ay ^ by);
-                if (MODE == PS_CL3 && Z > 1) {
+                if (M3 && Z > 1) {
                     const uint32_t dn = (f & PSF_ZWL) ? 0u : d0[i + 1];
                     const uint32_t dv = (f & PSF_ZW0) ? 0u : d0[i - 1];
                     const uint32_t zp = (D >> 8) | (dn << 24), zm = (D << 8) | (dv >> 24);
@@ -1398,6 +1437,32 @@ __global__ void __launch_bounds__(PS_TPB) k_plane(const float *__restrict__ n4,
             if (n_lb12) atomicAdd(&cnt_out[b * 2 + 1], n_lb12);
         }
     }
+}
+
+// a selection sweep's count (cnt[2 b], where classify puts n_defect) -> n_sel
+__global__ void k_sel_count_to_scalars(const unsigned long long *cnt, int64_t nb, VolScalars *sc) {
+    int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    sc[b].n_sel = (int64_t)cnt[b * 2];
+}
+
+// the k-means label map alone (vh_batch_download_defect asked for it after a selection that did
+// not write it): one thread per voxel
+__global__ void __launch_bounds__(VH_TPB) k_km_labels(const float *__restrict__ n4,
+                                                     const uint8_t *__restrict__ mask,
+                                                     const VolScalars *__restrict__ sc, int64_t V,
+                                                     uint8_t *km) {
+    const int64_t b = blockIdx.y;
+    const int64_t i = blockIdx.x * (int64_t)VH_TPB + threadIdx.x;
+    if (i >= V) return;
+    uint32_t lab = 0u;
+    if (mask[b * V + i] && sc[b].n_mask > 0) {   // (an empty study's cuts are undefined)
+        const int valid = sc[b].km_valid;
+        uint32_t ck[3], cv[3];
+        for (int j = 0; j < 3; ++j) { ck[j] = sc[b].km_cut[j]; cv[j] = (uint32_t)(valid >> j) & 1u; }
+        lab = km_label(f2key(n4[b * V + i]), ck, cv);
+    }
+    km[b * V + i] = (uint8_t)lab;
 }
 
 // plane-sweep geometry; false when a band of one row does not fit PS_K words per thread
@@ -1452,6 +1517,45 @@ void vh_launch_border(vh_batch *b, const uint8_t *d_in, uint8_t *d_out) {
     k_tile<false, false><<<grid, VH_TPB, lds, b->stream>>>(nullptr, b->d_mask, d_in, b->d_sc, 0.f,
                                                          b->R, b->C, b->Z, b->V, tz, nullptr,
                                                          d_out, nullptr, nullptr);
+    VH_CHECK_LAUNCH();
+}
+
+template <int MF>
+static void launch_plane_sel(vh_batch *b, const PsGeom &g, dim3 grid, size_t lds, const float *n4,
+                             float thresh, int source, uint8_t *km, unsigned long long *cnt) {
+    const bool vec = (g.Z & 3) == 0;
+    constexpr int M = PS_SEL + 3 * MF;
+    auto fn = source == VH_DEFECT_MEAN ? (vec ? k_plane<M + VH_DEFECT_MEAN, true> : k_plane<M + VH_DEFECT_MEAN, false>)
+              : source == VH_DEFECT_LB ? (vec ? k_plane<M + VH_DEFECT_LB, true> : k_plane<M + VH_DEFECT_LB, false>)
+                                       : (vec ? k_plane<M + VH_DEFECT_KM, true> : k_plane<M + VH_DEFECT_KM, false>);
+    fn<<<grid, PS_TPB, lds, b->stream>>>(n4, b->d_mask, nullptr, b->d_colrange, b->d_sc, thresh, g,
+                                         b->d_defect, b->d_border, km, cnt);
+}
+
+// The defect map and border of one thresholding, one sweep over the resident N4 and mask: the
+// same loads as classify (N4 in the masked column ranges, mask), two of its three stores.
+bool vh_launch_defect_select(vh_batch *b, const float *d_n4, float thresh, int source, int medfilt,
+                             uint8_t *km) {
+    PsGeom g; dim3 grid; size_t lds;
+    if (!plane_geometry(b, PS_SEL, g, grid, lds)) return false;
+    hipStream_t st = b->stream;
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(b->d_tilecnt);   // free after the sort
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 2 * b->nb, st));
+    {
+        ScopedKTimer tm(b, "defect_sel", (km ? 8.0 : 7.0) * (double)b->V);
+        if (medfilt == 0) launch_plane_sel<0>(b, g, grid, lds, d_n4, thresh, source, km, cnt);
+        else if (medfilt == 1) launch_plane_sel<1>(b, g, grid, lds, d_n4, thresh, source, km, cnt);
+        else launch_plane_sel<2>(b, g, grid, lds, d_n4, thresh, source, km, cnt);
+        VH_CHECK_LAUNCH();
+    }
+    k_sel_count_to_scalars<<<(unsigned)((b->nb + 63) / 64), 64, 0, st>>>(cnt, b->nb, b->d_sc);
+    VH_CHECK_LAUNCH();
+    return true;
+}
+
+void vh_launch_km_labels(vh_batch *b, const float *d_n4, uint8_t *km) {
+    k_km_labels<<<dim3((unsigned)((b->V + VH_TPB - 1) / VH_TPB), (unsigned)b->nb), VH_TPB, 0, b->stream>>>(
+        d_n4, b->d_mask, b->d_sc, b->V, km);
     VH_CHECK_LAUNCH();
 }
 
@@ -1809,11 +1913,21 @@ __global__ void __launch_bounds__(KM_TPB) k_kmeans(const uint32_t *__restrict__ 
     }
     if (t == 0) {   // VDP_km: the lowest non-empty cluster
         int64_t low = 0;
+        int lowj = 0;
         for (int j = KM_K - 1; j >= 0; --j)
-            if (s_cut[j + 1] > s_cut[j]) low = s_cut[j + 1] - s_cut[j];
+            if (s_cut[j + 1] > s_cut[j]) { low = s_cut[j + 1] - s_cut[j]; lowj = j; }
         sc[b].n_km0 = low;
         sc[b].km_iters = it;
         for (int j = 0; j < KM_K; ++j) sc[b].km_c[j] = s_c[j];
+        // the final cuts as keys (the defect selection labels a voxel by its value alone)
+        int valid = 0;
+        for (int j = 1; j < KM_K; ++j) {
+            const bool in = s_cut[j] < n;
+            sc[b].km_cut[j - 1] = k[in ? s_cut[j] : n - 1];
+            valid |= in ? 1 << (j - 1) : 0;
+        }
+        sc[b].km_valid = valid;
+        sc[b].km_low = lowj;
     }
 }
 
@@ -2072,14 +2186,27 @@ __global__ void __launch_bounds__(KM_TPB) k_kmeans_s(const uint32_t *__restrict_
         km_update<true>(k, cut, sum, c);   // means, empty-cluster relocation, sort
     }
     if (lane == 0) {   // VDP_km: the lowest non-empty cluster
-        int low = 0;
+        int low = 0, lowj = 0;
 #pragma unroll
         for (int j = KM_K - 1; j >= 0; --j)
-            if (cut[j + 1] > cut[j]) low = cut[j + 1] - cut[j];
+            if (cut[j + 1] > cut[j]) { low = cut[j + 1] - cut[j]; lowj = j; }
         sc[b].n_km0 = low;
         sc[b].km_iters = it;
 #pragma unroll
         for (int j = 0; j < KM_K; ++j) sc[b].km_c[j] = c[j];
+        // the final cuts as keys (the defect selection labels a voxel by its value alone); the
+        // three loads at clamped indices, in flight together
+        uint32_t ck[KM_K - 1];
+        int valid = 0;
+#pragma unroll
+        for (int j = 1; j < KM_K; ++j) ck[j - 1] = k[cut[j] < n ? cut[j] : n - 1];
+#pragma unroll
+        for (int j = 1; j < KM_K; ++j) {
+            sc[b].km_cut[j - 1] = ck[j - 1];
+            valid |= cut[j] < n ? 1 << (j - 1) : 0;
+        }
+        sc[b].km_valid = valid;
+        sc[b].km_low = lowj;
 #ifdef KM_PROF
         const uint64_t kp2 = wall_clock64();
         if (b < 4)

@@ -89,6 +89,14 @@ struct VolScalars {
     int32_t row_lo, row_hi;  // first / last row holding any masked voxel
     int64_t n_ci;            // defect voxels for CI
     double ci_scalar;
+    // k-means' final partition for the defect selection (vh_batch_select_defect), appended so the
+    // fields above keep their offsets: the sortable key at cut j + 1 (the smallest value of cluster
+    // j + 1), valid where bit j of km_valid is set (cut j + 1 < n); the lowest non-empty cluster
+    uint32_t km_cut[3];
+    int32_t km_valid;
+    int32_t km_low;
+    int32_t pad1;
+    int64_t n_sel;           // voxels of the last selected defect map
 };
 
 // Per-volume N4 iteration state.
@@ -195,6 +203,11 @@ struct vh_batch {
     uint8_t *d_mask = nullptr;
     float *d_n4 = nullptr;
     uint8_t *d_defect = nullptr, *d_border = nullptr, *d_lb = nullptr;
+    // vh_batch_select_defect
+    uint8_t *d_km = nullptr;         // [nb][V] k-means labels (0 off-mask, else 1 + cluster), on first demand
+    const float *d_n4_last = nullptr;   // the N4 volume the last run's chain read (d_hp or d_n4)
+    bool km_valid = false;           // d_km holds the last run's labels
+    bool sel_valid = false;          // a selection replaced the last run's maps (VolScalars::n_sel counts it)
     // mask statistics
     int32_t *d_colrange = nullptr;   // [nb][CZ][2]  first/last masked row of each (col, slice) column
     int32_t *d_colcount = nullptr;   // [nb][CZ]
@@ -335,6 +348,12 @@ void vh_launch_mask_stats(vh_batch *b);
 void vh_launch_vdp_chain(vh_batch *b, const float *d_n4, const vh_run_opts &o);
 void vh_launch_snr(vh_batch *b);
 void vh_launch_border(vh_batch *b, const uint8_t *d_in, uint8_t *d_out);
+// the defect map and border of one thresholding (VH_DEFECT_*) from the resident N4 and scalars; km
+// (nullable) also takes the k-means labels.  False, with nothing launched, when the shape has no
+// plane-sweep geometry.
+bool vh_launch_defect_select(vh_batch *b, const float *d_n4, float thresh, int source, int medfilt,
+                             uint8_t *km);
+void vh_launch_km_labels(vh_batch *b, const float *d_n4, uint8_t *km);
 void vh_launch_n4(vh_batch *b, const vh_n4_params &prm);
 void vh_n4_prepare_tables(vh_batch *b, const vh_n4_params &prm);
 vh_ci_table *vh_ci_table_build(vh_ctx *ctx, int64_t R, int64_t C, const int16_t *offs, const uint8_t *dup,
