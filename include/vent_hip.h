@@ -28,6 +28,13 @@
  *                map, border and count of the linear-binning or k-means VDP (or the mean-anchored
  *                one again), and the k-means label map, so calculate_CI / exportDICOM / screenShot
  *                can show the defect any of calculate_VDP's three percentages counts (build-defined)
+ *   vh_batch_overlay / vh_batch_download_overlay  exportDICOM's pixel data (Vent_Analysis.py:387-393)
+ *                of every study from the batch's resident N4 and defect maps
+ *   vh_batch_montage_layout / vh_batch_montage / vh_batch_download_montage  cropToData(mask, border=5)
+ *                (Vent_Analysis.py:430-456) and screenShot's montage array (:467-495) of every study
+ *                from the resident buffers, with calculateBorder(mask) (:225-231) evaluated in place;
+ *                only pixels come back.  Their kernel-timing classes are "overlay_b" and "montage_b"
+ *                (vh_batch_kernel_time reads them; vh_batch_kernel_names does not list them)
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -252,6 +259,45 @@ int vh_montage(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, const void *proton,
                const void *hp, int hp_is64, const float *n4, const uint8_t *mask_border,
                const uint8_t *defect, const double *ci, const double *parula, int64_t prow,
                const int64_t crop[6], uint8_t *image);
+
+/* ---- the same renderings of a device-resident batch ------------------------------------------
+ * They read what vh_batch_run left resident and bring back pixels only; nothing the run, vh_batch_ci
+ * or the selection calls wrote is changed.  Each needs a vh_batch_run on the batch (VH_ERR_ARG
+ * otherwise); a new run discards what they enqueued.
+ *
+ * vh_batch_overlay enqueues vh_overlay for every study: N4 is the volume the last run's chain read
+ * (HPvent when do_n4 = 0), defect the resident map as it stands (the run's, vh_batch_set_defect's or
+ * vh_batch_select_defect's).  VH_ERR_ARG, with nothing enqueued, for more than 65535 studies or rows.
+ * vh_batch_download_overlay waits; rgb uint8 [nb][Z][R][C][3], study i's block byte for byte what
+ * vh_overlay returns for that study's downloaded N4 and defect map. */
+int vh_batch_overlay(vh_batch *b);
+int vh_batch_download_overlay(vh_batch *b, uint8_t *rgb);
+/* Where every study's montage lies (waits; the result is kept until the next run).  crop[i] =
+ * {r0, nr, c0, nc, s0, ns} is cropToData(mask, border=5) of study i's resident mask: a row, column
+ * or slice is non-empty when its mask sum is > 0, index 0 never counts (the reference's quirk), rows
+ * and columns widen by 5 and clamp, slices do not.  Study i's image, uint8 [7 nr][ns nc][3], starts
+ * at byte offset[i] of the compact buffer (a multiple of 64) and has 21 nr nc ns bytes; offset[nb] is
+ * the buffer's size.  A study for which the reference raises IndexError (no counted row, column or
+ * slice: an empty mask, a mask only at index 0) has status[i] = VH_ERR_EMPTY, a crop of zeros and no
+ * image; the call still returns VH_OK.  All three outputs are nullable. */
+int vh_batch_montage_layout(vh_batch *b, int64_t *crop /* [nb][6] */, int64_t *offset /* [nb + 1] */,
+                            int32_t *status /* [nb] */);
+/* Enqueue vh_montage for every study over its crop: proton float32 [nb][V] (NULL: zeros, what the
+ * class substitutes for a missing proton image), HPvent and N4 the resident volumes (N4 as for
+ * vh_batch_overlay), each normalised in float32 over the crop; the mask border is
+ * calculateBorder(mask) != 0 of the resident mask (0/v masks included), the defect panel shows
+ * defect != 0.  The CI panel is drawn only when vh_batch_ci was enqueued after the last change of the
+ * resident defect maps (vh_batch_run, vh_batch_set_defect, vh_batch_select_defect), from exactly the
+ * float64 values vh_batch_download_ci's ci_array holds; otherwise it is the reference's blank CI
+ * panel (N4).  parula float64 [prow][3]; VH_ERR_ARG when prow < 1.  The first call after a run
+ * computes the layout if vh_batch_montage_layout has not (it then waits for the stream once).  proton
+ * and parula stay valid until the next waiting call on the batch. */
+int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int64_t prow);
+/* Waits.  image: offset[nb] bytes, laid out as vh_batch_montage_layout says (the padding between
+ * images is not written).  status[i] (nullable): VH_OK, VH_ERR_EMPTY, or VH_ERR_INDEX when a CI colour
+ * index int(CI * 64 / 40) of the study's crop reached prow (the IndexError of Vent_Analysis.py:482-484):
+ * that study's image bytes are unspecified, the other studies are unaffected. */
+int vh_batch_download_montage(vh_batch *b, uint8_t *image, int32_t *status);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

@@ -1,0 +1,173 @@
+"""GPU: the renderings of a device-resident batch (Batch.overlay / montage_layout / montage) against
+the CPU restatement of exportDICOM, cropToData and screenShot (oracle.export_oracle) on what the batch
+itself downloads.  Every comparison is of uint8 pixels or integers: exact."""
+import numpy as np
+import pytest
+
+from vent_analysis_amd import _lib
+
+import batch_render_ref as BR
+
+pytestmark = pytest.mark.gpu
+
+PAL = BR.parula()
+
+
+def run_batch(hp, mk, **kw):
+    B = _lib.Batch(*hp.shape[1:], hp.shape[0])
+    B.upload(hp, mk)
+    kw.setdefault("do_n4", False)
+    B.run(B.options(vox=BR.VOX, **kw))
+    return B
+
+
+def check_render(B, hp, mk, proton=None, ci=None, pal=PAL, index_error=()):
+    """Layout, overlay and montage of the batch as it stands against the oracle on the downloaded N4
+    and defect maps.  Returns the number of montages compared."""
+    n4, d, _, _, _ = B.download(n4=True)
+    nb = hp.shape[0]
+    ecrop, estatus = BR.expected_layout(mk)
+    crop, off, status = B.montage_layout()
+    assert crop.dtype == np.int64 and off.dtype == np.int64 and status.dtype == np.int32
+    assert np.array_equal(crop, ecrop) and np.array_equal(status, estatus)
+    size = 21 * crop[:, 1] * crop[:, 3] * crop[:, 5]
+    assert off[0] == 0 and np.all(off % 4 == 0) and np.all(np.diff(off) >= size)
+    ov = B.overlay()
+    assert ov.shape == (nb, hp.shape[3], hp.shape[1], hp.shape[2], 3) and ov.dtype == np.uint8
+    for q in range(nb):
+        assert np.array_equal(ov[q], BR.overlay_ref(n4[q], d[q])), q
+    imgs, mstatus = B.montage(pal, proton)
+    compared = 0
+    for q in range(nb):
+        if estatus[q] != BR.VH_OK:
+            assert mstatus[q] == BR.VH_ERR_EMPTY and imgs[q] is None, q
+            continue
+        if q in index_error:
+            assert mstatus[q] == BR.VH_ERR_INDEX and imgs[q] is None, q
+            continue
+        assert mstatus[q] == BR.VH_OK, (q, mstatus[q])
+        ref = BR.montage_ref(None if proton is None else proton[q], hp[q], n4[q], mk[q], d[q],
+                             None if ci is None else ci[q], pal)
+        assert imgs[q].shape == ref.shape and imgs[q].dtype == np.uint8, q
+        assert np.array_equal(imgs[q], ref), (q, int((imgs[q] != ref).sum()))
+        compared += 1
+    return compared
+
+
+@pytest.mark.parametrize("with_proton", [False, True], ids=["no-proton", "proton"])
+def test_mixed_batch(with_proton):
+    hp, mk, proton = BR.mixed_batch()
+    B = run_batch(hp, mk)
+    n4 = B.download(n4=True)[0]
+    assert np.array_equal(n4, hp)                      # do_n4 = 0: the chain read HPvent
+    assert np.ptp(hp[5]) == 0 and hp[5, 0, 0, 0] == 2  # the flat study
+    _, _, status = B.montage_layout()
+    assert int((status == BR.VH_ERR_EMPTY).sum()) == 2
+    assert check_render(B, hp, mk, proton if with_proton else None) == 5
+    B.close()
+
+
+@pytest.mark.parametrize("shape,n", [((19, 70, 5), 3), ((24, 20, 70), 3), ((128, 128, 24), 2)], ids=str)
+def test_shapes(shape, n):
+    hp, mk, proton = BR.shape_batch(shape)
+    B = run_batch(hp, mk)
+    assert check_render(B, hp, mk, proton) == n
+    assert check_render(B, hp, mk, None) == n
+    B.close()
+
+
+def test_n4_panels_show_the_runs_n4():
+    hp, mk = BR.n4_batch()
+    B = run_batch(hp, mk, do_n4=True)
+    n4 = B.download(n4=True)[0]
+    for q in range(3):   # the test can tell N4 from HPvent, also after the crop's normalisation
+        assert not np.array_equal(n4[q], hp[q])
+        assert not np.array_equal(BR.montage_ref(None, hp[q], n4[q], mk[q], np.zeros_like(mk[q]), None, PAL),
+                                  BR.montage_ref(None, hp[q], hp[q], mk[q], np.zeros_like(mk[q]), None, PAL))
+    assert check_render(B, hp, mk) == 3
+    B.close()
+
+
+def test_selected_and_uploaded_defects_are_shown():
+    hp, mk, proton = BR.mixed_batch()
+    B = run_batch(hp, mk)
+    d0 = B.download()[1]
+    B.select_defect("lb", 0)
+    d1 = B.download_defect()[0]
+    assert not np.array_equal(d0, d1) and d1.any()
+    assert check_render(B, hp, mk, proton) == 5
+    d2 = d0.copy()
+    d2[:, 10:30:3, 8:30:2, 2:7] = 2    # neither 0 nor 1: black in the overlay, defect in the montage
+    d2[:, 18:24, 15:22, 4] = 1
+    B.upload_defect(d2)
+    assert np.array_equal(B.download()[1], d2)
+    assert check_render(B, hp, mk, proton) == 5
+    B.close()
+
+
+def test_ci_panel():
+    hp, mk, proton = BR.mixed_batch()
+    B = run_batch(hp, mk)
+    B.select_defect("lb", 1)
+    B.ci(BR.VOX, Rmax=12)
+    ci, _, cst = B.download_ci("f64")
+    assert (ci > 0).sum() > 100 and len(np.unique(ci)) > 3
+    assert check_render(B, hp, mk, proton, ci=ci) == 5
+    # a truncated colour table: the study whose largest colour index is k, and every study reaching
+    # k, reports VH_ERR_INDEX; the others stay right
+    crop, _ = BR.expected_layout(mk)
+    top = []
+    for q in range(hp.shape[0]):
+        r0, nr, c0, nc, s0, ns = crop[q]
+        v = ci[q, r0:r0 + nr, c0:c0 + nc, s0:s0 + ns]
+        top.append(int(v.max() * 64 / 40) if v.size else -1)
+    live = [q for q in range(hp.shape[0]) if top[q] > 0]
+    k = sorted({top[q] for q in live})[-1]
+    bad = {q for q in live if top[q] >= k}
+    assert 1 <= k < PAL.shape[0] and bad and len(bad) < 5
+    assert check_render(B, hp, mk, proton, ci=ci, pal=PAL[:k], index_error=bad) == 5 - len(bad) >= 1
+    # a selection after ci(): the panel is the blank one again; ci() once more draws it
+    B.select_defect("mean", 1)
+    assert check_render(B, hp, mk, proton, ci=None) == 5
+    assert np.array_equal(B.download_ci("f64")[0], ci)   # download_ci is as before: the last ci()'s map
+    B.ci(BR.VOX, Rmax=12)
+    assert check_render(B, hp, mk, proton, ci=B.download_ci("f64")[0]) == 5
+    B.close()
+
+
+def test_call_order_errors():
+    hp, mk, _ = BR.shape_batch((19, 70, 5))
+    B = _lib.Batch(*hp.shape[1:], hp.shape[0])
+    B.upload(hp, mk)
+    for call in (B.overlay, B.montage_layout, lambda: B.montage(PAL)):
+        with pytest.raises(ValueError):
+            call()
+    B.run(B.options(do_n4=False, vox=BR.VOX))
+    with pytest.raises(ValueError):
+        B.montage(np.zeros((0, 3)))
+    assert B.montage(PAL)[1].tolist() == [0, 0, 0]
+    B.close()
+
+
+def test_deterministic_and_leaves_the_run_state():
+    hp, mk, proton = BR.mixed_batch()
+    B = run_batch(hp, mk, do_cohort=True)
+    B.ci(BR.VOX, Rmax=12)
+
+    def state():
+        n4, d, bo, lb, res = B.download(n4=True)
+        dd, bb, cnt, km = B.download_defect(km=True)
+        scal = [(r.vdp, r.vdp_lb, r.vdp_km, r.n_mask, r.n_defect, r.p99) for r in res]
+        return [n4, d, bo, lb, dd, bb, cnt, km, B.km_cuts(), B.cohort_hist(), *B.download_ci("shell")], scal
+
+    before, scal0 = state()
+    ov1, (im1, st1) = B.overlay(), B.montage(PAL, proton)
+    ov2, (im2, st2) = B.overlay(), B.montage(PAL, proton)
+    assert np.array_equal(ov1, ov2) and np.array_equal(st1, st2)
+    for a, b in zip(im1, im2):
+        assert (a is None and b is None) or np.array_equal(a, b)
+    after, scal1 = state()
+    assert repr(scal0) == repr(scal1)   # (NaN-safe)
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y, equal_nan=True)
+    B.close()

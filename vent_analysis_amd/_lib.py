@@ -110,6 +110,11 @@ _SIGS = {
     "vh_overlay": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P], ct.c_int),
     "vh_montage": ([_P, _I64, _I64, _I64, _P, ct.c_int, _P, ct.c_int, _P, _P, _P, _P, _P, _I64, _P,
                     _P], ct.c_int),
+    "vh_batch_overlay": ([_P], ct.c_int),
+    "vh_batch_download_overlay": ([_P, _P], ct.c_int),
+    "vh_batch_montage_layout": ([_P, _P, _P, _P], ct.c_int),
+    "vh_batch_montage": ([_P, _P, _P, _I64], ct.c_int),
+    "vh_batch_download_montage": ([_P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -533,6 +538,23 @@ def montage(proton, hp, n4, mask_border, defect, ci, parula, crop, device=0):
     return img
 
 
+def montage_views(buf, crop, offset, status):
+    """Batch.montage's images out of the compact buffer: study i's uint8 [7 nr][ns nc][3] is the
+    21 nr nc ns bytes at offset[i] (crop[i] = r0, nr, c0, nc, s0, ns); None where status[i] != VH_OK.
+    Views of ``buf``, no copies."""
+    out = []
+    for (r0, nr, c0, nc, s0, ns), o, st in zip(np.asarray(crop).tolist(), np.asarray(offset).tolist(),
+                                               np.asarray(status).tolist()):
+        if st != VH_OK:
+            out.append(None)
+            continue
+        n = 21 * nr * nc * ns
+        if o + n > buf.shape[0]:
+            raise ValueError(f"montage_views: an image of {n} bytes at {o} is past the buffer's {buf.shape[0]}")
+        out.append(buf[o:o + n].reshape(7 * nr, ns * nc, 3))
+    return out
+
+
 def recon(raw_k, device=0):
     """process_RAW's image (vh_recon, Vent_Analysis.py:537-540): complex k-space [n0][n1][nz] ->
     complex128 [n1][n0][nz] = transpose(fftshift(fft2(fftshift(slice))), (1, 0, 2))[:, ::-1, :].
@@ -685,6 +707,56 @@ class Batch:
                        "vh_batch_download_ci")
         sc[status != VH_OK] = np.nan
         return (f64 if maps == "f64" else sh), sc, status
+
+    def overlay(self):
+        """exportDICOM's pixel data of every study (vh_batch_overlay): uint8 [B][Z][R][C][3], rendered
+        on the device from the N4 the last run's chain read and the resident defect maps (the run's,
+        upload_defect's or select_defect's) -- study i's block equals _lib.overlay of its downloaded
+        N4 and defect map.  Needs a run (ValueError otherwise)."""
+        B, R, C, Z = self.shape
+        self.ctx.check(self.L.vh_batch_overlay(self.h), "vh_batch_overlay")
+        out = self.ctx.pinned.array((B, Z, R, C, 3), np.uint8)   # page-locked: the D2H runs at the link rate
+        self.ctx.check(self.L.vh_batch_download_overlay(self.h, _ptr(out)), "vh_batch_download_overlay")
+        return out
+
+    def montage_layout(self):
+        """(crop int64 [B][6], offset int64 [B + 1], status int32 [B]) of the batch's montages
+        (vh_batch_montage_layout): crop[i] = (r0, nr, c0, nc, s0, ns) is cropToData(mask, border=5) of
+        study i, offset[i] the byte at which its image starts in the compact buffer, offset[B] the
+        buffer's size; status[i] is VH_ERR_EMPTY (zeros, no image) where the reference would raise
+        IndexError.  Needs a run."""
+        B = self.shape[0]
+        crop = np.zeros((B, 6), np.int64)
+        off = np.zeros(B + 1, np.int64)
+        status = np.zeros(B, np.int32)
+        self.ctx.check(self.L.vh_batch_montage_layout(self.h, _ptr(crop), _ptr(off), _ptr(status)),
+                       "vh_batch_montage_layout")
+        return crop, off, status
+
+    def montage(self, parula, proton=None):
+        """screenShot's montage array of every study, rendered on the device from the resident
+        HPvent, N4, mask and defect maps (vh_batch_montage): (images, status).  images[i] is uint8
+        [7 nr][ns nc][3] over study i's crop (a view of one compact buffer) or None where status[i] !=
+        VH_OK: VH_ERR_EMPTY (no crop) or VH_ERR_INDEX (a CI colour index past ``parula``).  The CI panel
+        is drawn when ci() was enqueued after the last run / upload_defect / select_defect, else it is
+        the blank CI panel.  ``proton`` [B][R][C][Z] (None: zeros) is converted to float32, so a
+        float64 proton is normalised in float32 here, unlike Vent_Analysis.screenShot, which
+        normalises a float64 proton in float64."""
+        pal = np.ascontiguousarray(parula, dtype=np.float64)
+        if pal.ndim != 2 or pal.shape[1] != 3:
+            raise ValueError(f"montage: parula must be [rows][3], got shape {pal.shape}")
+        p = None
+        if proton is not None:
+            p = np.ascontiguousarray(proton, dtype=np.float32)
+            if p.shape != self.shape:
+                raise ValueError(f"batch expects {self.shape}")
+        crop, off, lstatus = self.montage_layout()
+        self.ctx.check(self.L.vh_batch_montage(self.h, _ptr(p), _ptr(pal), pal.shape[0]), "vh_batch_montage")
+        buf = self.ctx.pinned.array((int(off[-1]),), np.uint8) if off[-1] else np.empty(0, np.uint8)
+        status = np.zeros(self.shape[0], np.int32)
+        self.ctx.check(self.L.vh_batch_download_montage(self.h, _ptr(buf), _ptr(status)),
+                       "vh_batch_download_montage")
+        return montage_views(buf, crop, off, status), status
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

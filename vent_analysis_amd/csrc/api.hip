@@ -159,6 +159,8 @@ static void batch_free(vh_batch *b) {
     dfree(b->d_ci_status);
     dfree(b->d_ci_count); dfree(b->d_ci_map);
     dfree(b->d_ci_shell16); dfree(b->d_ci_next); dfree(b->d_ci_radii);
+    dfree(b->d_ov_rgb); dfree(b->d_ov_mm); dfree(b->d_proton); dfree(b->d_mt_crop); dfree(b->d_mt_st);
+    dfree(b->d_mt_keys); dfree(b->d_mt_flag); dfree(b->d_mt_parula); dfree(b->d_mt_img);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     if (b->st_n4) (void)hipStreamDestroy(b->st_n4);
     if (b->ev_n4_pre) (void)hipEventDestroy(b->ev_n4_pre);
@@ -294,6 +296,10 @@ static void batch_run(vh_batch *b, const vh_run_opts &o, int n4_src) {
     b->d_n4_last = n4;
     b->km_valid = false;
     b->sel_valid = false;
+    b->ci_fresh = false;          // the run replaced the defect maps, and the mask statistics
+    b->mt_layout_valid = false;
+    b->ov_valid = false;
+    b->mt_valid = false;
 }
 
 // the study kernel's spin-wait watchdog (n4_study.hip st_spin) leaves N4State.active = -2
@@ -781,6 +787,7 @@ int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox) {
         b->ci_nbs = t->nbs;
         b->ci_minvox = minvox;
         b->have_ci = true;
+        b->ci_fresh = true;
     })
 }
 
@@ -793,6 +800,7 @@ int vh_batch_set_defect(vh_batch *b, const uint8_t *defect) {
         HIP_TRY(hipStreamSynchronize(b->stream));
         b->have_defect = true;
         b->sel_valid = false;
+        b->ci_fresh = false;
     })
 }
 
@@ -813,6 +821,7 @@ static void batch_select(vh_batch *b, int source, int medfilt) {
         throw VhError{VH_ERR_ARG, "vh_batch_select_defect: this shape has no plane-sweep geometry"};
     if (km) b->km_valid = true;
     b->sel_valid = true;
+    b->ci_fresh = false;
 }
 
 static void batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count) {
@@ -1050,6 +1059,140 @@ int vh_montage(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, const void *proton,
         vh_batch *b = scratch_batch(ctx, R, C, Z, 1);
         vh_montage_run(b->stream, R, C, Z, proton, proton_is64, hp, hp_is64, n4, mask_border, defect,
                        ci, parula, prow, crop, image);
+    })
+}
+
+// ---- the renderings of a device-resident batch --------------------------------------------------
+// exportDICOM's frames of every study from the resident N4 (the volume the last run's chain read)
+// and defect maps: vh_overlay's kernels on the batch's own buffers.  The frames go to a buffer of
+// their own, allocated on first demand like d_km: a rendering writes nothing
+// another call on the batch reads.
+int vh_batch_overlay(vh_batch *b) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+        if (b->nb > 65535 || b->R > 65535) throw VhError{VH_ERR_ARG, "overlay: batch or rows out of range"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        const size_t NV = (size_t)b->nb * b->V;
+        if (!b->d_ov_rgb) dalloc(&b->d_ov_rgb, 3 * NV);
+        if (!b->d_ov_mm) dalloc(&b->d_ov_mm, 2 * (size_t)b->nb);
+        // N4 twice (min/max, then the frames), the defect map, 3 bytes out
+        ScopedKTimer tm(b, "overlay_b", 12.0 * (double)NV);
+        vh_overlay_launch(b->stream, b->d_n4_last, b->d_defect, b->R, b->C, b->Z, b->nb, b->d_ov_mm, b->d_ov_rgb);
+        b->ov_valid = true;
+    })
+}
+
+int vh_batch_download_overlay(vh_batch *b, uint8_t *rgb) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!rgb) throw VhError{VH_ERR_ARG, "null buffer"};
+        if (!b->ov_valid) throw VhError{VH_ERR_ARG, "vh_batch_overlay has not been called since the last run"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        d2h_on_stream(b, rgb, b->d_ov_rgb, 3 * (size_t)b->nb * b->V);
+    })
+}
+
+// cropToData of every resident mask and the compact buffer's layout; cached until the next run.
+// One small kernel, a copy of nb x 32 bytes back, the prefix on the host, nb + 1 records up.
+static void batch_montage_layout(vh_batch *b) {
+    if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    if (b->mt_layout_valid) return;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    const int64_t nb = b->nb;
+    if (!b->d_mt_crop) dalloc(&b->d_mt_crop, (size_t)nb * 8);
+    if (!b->d_mt_st) dalloc(&b->d_mt_st, (size_t)nb + 1);
+    vh_crop_layout_launch(b);
+    std::vector<int32_t> h((size_t)nb * 8);
+    d2h_on_stream(b, h.data(), b->d_mt_crop, sizeof(int32_t) * h.size());
+    b->mt_st.assign((size_t)nb + 1, MtStudy{});
+    b->mt_status.assign((size_t)nb, VH_OK);
+    int64_t off = 0, wg = 0;
+    for (int64_t i = 0; i < nb; ++i) {
+        MtStudy &s = b->mt_st[i];
+        const int32_t *c = &h[(size_t)i * 8];
+        s.r0 = c[0]; s.nr = c[1]; s.c0 = c[2]; s.nc = c[3]; s.s0 = c[4]; s.ns = c[5];
+        b->mt_status[i] = c[6];
+        s.ncc = (s.nc + VH_MT_COLS - 1) / VH_MT_COLS;
+        s.nzc = (s.ns + VH_MT_ZC - 1) / VH_MT_ZC;
+        s.off = off;
+        s.wg0 = wg;
+        const int64_t bytes = (int64_t)21 * s.nr * s.nc * s.ns;
+        off += (bytes + VH_MT_ALIGN - 1) / VH_MT_ALIGN * VH_MT_ALIGN;
+        wg += (int64_t)s.nr * s.ncc * s.nzc;
+    }
+    if (wg > 0x7fffffff) throw VhError{VH_ERR_ARG, "montage: too many crop rows for one launch"};
+    b->mt_st[nb].off = off;
+    b->mt_st[nb].wg0 = wg;
+    HIP_TRY(hipMemcpyAsync(b->d_mt_st, b->mt_st.data(), sizeof(MtStudy) * (nb + 1), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->mt_layout_valid = true;
+}
+
+int vh_batch_montage_layout(vh_batch *b, int64_t *crop, int64_t *offset, int32_t *status) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        batch_montage_layout(b);
+        for (int64_t i = 0; i < b->nb; ++i) {
+            const MtStudy &s = b->mt_st[i];
+            const int64_t c[6] = {s.r0, s.nr, s.c0, s.nc, s.s0, s.ns};
+            if (crop) memcpy(crop + 6 * i, c, sizeof c);
+            if (offset) offset[i] = s.off;
+            if (status) status[i] = b->mt_status[i];
+        }
+        if (offset) offset[b->nb] = b->mt_st[b->nb].off;
+    })
+}
+
+// screenShot's montage of every study, rendered from the resident buffers (export.hip k_montage_b).
+// Enqueue only once the layout is cached (vh_batch_montage_layout; otherwise it is computed here,
+// which waits for the stream once).  The CI panel is drawn when vh_batch_ci was enqueued after the
+// last change of the resident defect maps.
+int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int64_t prow) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+        if (!parula || prow < 1) throw VhError{VH_ERR_ARG, "montage: empty colour table"};
+        batch_montage_layout(b);
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        const size_t NV = (size_t)b->nb * b->V;
+        const int64_t total = b->mt_st[b->nb].off;
+        if (!b->d_mt_keys) dalloc(&b->d_mt_keys, 6 * (size_t)b->nb);
+        if (!b->d_mt_flag) dalloc(&b->d_mt_flag, (size_t)b->nb);
+        if (prow > b->mt_prow_cap) {
+            dfree(b->d_mt_parula);
+            b->mt_prow_cap = 0;
+            dalloc(&b->d_mt_parula, 3 * (size_t)prow);
+            b->mt_prow_cap = prow;
+        }
+        if (total > b->mt_img_cap) {
+            HIP_TRY(hipStreamSynchronize(b->stream));   // an earlier montage may still be writing
+            dfree(b->d_mt_img);
+            b->mt_img_cap = 0;
+            dalloc(&b->d_mt_img, (size_t)total);
+            b->mt_img_cap = total;
+        }
+        if (proton && !b->d_proton) dalloc(&b->d_proton, NV);
+        HIP_TRY(hipMemcpyAsync(b->d_mt_parula, parula, sizeof(double) * 3 * prow, hipMemcpyHostToDevice, b->stream));
+        if (proton) HIP_TRY(hipMemcpyAsync(b->d_proton, proton, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
+        vh_montage_b_launch(b, proton != nullptr, prow, b->ci_fresh);
+        b->mt_valid = true;
+    })
+}
+
+int vh_batch_download_montage(vh_batch *b, uint8_t *image, int32_t *status) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->mt_valid) throw VhError{VH_ERR_ARG, "vh_batch_montage has not been called since the last run"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        const int64_t total = b->mt_st[b->nb].off;
+        if (total > 0 && !image) throw VhError{VH_ERR_ARG, "null buffer"};
+        if (total > 0) HIP_TRY(hipMemcpyAsync(image, b->d_mt_img, (size_t)total, hipMemcpyDeviceToHost, b->stream));
+        std::vector<int32_t> flag((size_t)b->nb);
+        d2h_on_stream(b, flag.data(), b->d_mt_flag, sizeof(int32_t) * flag.size());   // synchronises the stream
+        if (status)
+            for (int64_t i = 0; i < b->nb; ++i)
+                status[i] = b->mt_status[i] != VH_OK ? b->mt_status[i] : flag[i] ? VH_ERR_INDEX : VH_OK;
     })
 }
 

@@ -325,3 +325,297 @@ void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *
     if (herr & 1) throw VhError{VH_ERR_INDEX, "CI colour index out of range of the colour table "
                                               "(int(CI*64/40), Vent_Analysis.py:482-484)"};
 }
+
+// ---- the montages of a device-resident batch (vh_batch_montage) -------------------------------
+// Everything k_montage reads is resident after vh_batch_run: d_hp, d_n4_last, d_mask, d_defect and
+// (after vh_batch_ci) the int16 shell map with the table's radii.  Three kernels serve the whole
+// batch: k_crop_layout (cropToData of every mask, from the run's mask statistics), k_crop_minmax_b
+// (the crop minima / maxima of proton, HPvent and N4) and k_montage_b (all studies' pixels over their
+// ragged crops, into one compact buffer).
+#define MT_COLS VH_MT_COLS   // crop columns per workgroup
+#define MT_ZC VH_MT_ZC       // crop slices per workgroup
+#define MT_DRAWN 5     // panels 2..6 are composed; 0 and 1 are blank
+
+// cropToData(mask, border=5) (Vent_Analysis.py:430-456) of every study, one workgroup each, from
+// the flags and counts the run's mask pass left (mask != 0, which is what sum > 0 says of a uint8
+// mask).  Index 0 never counts as non-empty (the reference multiplies the flags by the index list);
+// rows and columns widen by 5 and clamp, slices do not.  A study with no counted row, column or
+// slice -- the reference's IndexError -- gets zeros and status VH_ERR_EMPTY.  The column flags are
+// derived from colcount: k_mask_finish may keep its own in LDS.
+__global__ __launch_bounds__(VH_TPB) void k_crop_layout(const uint8_t *__restrict__ rowany,
+                                                        const uint8_t *__restrict__ sliceany,
+                                                        const int32_t *__restrict__ colcount,
+                                                        int64_t R, int64_t C, int64_t Z,
+                                                        int32_t *__restrict__ crop) {
+    __shared__ int32_t s_lo[3], s_hi[3];
+    const int64_t b = blockIdx.x, CZ = C * Z;
+    if (threadIdx.x < 3) { s_lo[threadIdx.x] = INT_MAX; s_hi[threadIdx.x] = -1; }
+    __syncthreads();
+    int32_t lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+    for (int64_t r = 1 + threadIdx.x; r < R; r += VH_TPB)
+        if (rowany[b * R + r]) { lo[0] = min(lo[0], (int32_t)r); hi[0] = max(hi[0], (int32_t)r); }
+    for (int64_t i = Z + threadIdx.x; i < CZ; i += VH_TPB)   // columns 1 .. C - 1
+        if (colcount[b * CZ + i] > 0) {
+            const int32_t c = (int32_t)((uint32_t)i / (uint32_t)Z);
+            lo[1] = min(lo[1], c); hi[1] = max(hi[1], c);
+        }
+    for (int64_t z = 1 + threadIdx.x; z < Z; z += VH_TPB)
+        if (sliceany[b * Z + z]) { lo[2] = min(lo[2], (int32_t)z); hi[2] = max(hi[2], (int32_t)z); }
+    for (int q = 0; q < 3; ++q)
+        if (hi[q] >= 0) { atomicMin(&s_lo[q], lo[q]); atomicMax(&s_hi[q], hi[q]); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t *o = crop + b * 8;
+        const bool ok = s_hi[0] >= 0 && s_hi[1] >= 0 && s_hi[2] >= 0;
+        const int32_t r0 = max(s_lo[0] - 5, 0), r1 = min(s_hi[0] + 6, (int32_t)R);
+        const int32_t c0 = max(s_lo[1] - 5, 0), c1 = min(s_hi[1] + 6, (int32_t)C);
+        o[0] = ok ? r0 : 0; o[1] = ok ? r1 - r0 : 0;
+        o[2] = ok ? c0 : 0; o[3] = ok ? c1 - c0 : 0;
+        o[4] = ok ? s_lo[2] : 0; o[5] = ok ? s_hi[2] + 1 - s_lo[2] : 0;
+        o[6] = ok ? VH_OK : VH_ERR_EMPTY;
+        o[7] = 0;
+    }
+}
+
+void vh_crop_layout_launch(vh_batch *b) {
+    k_crop_layout<<<(unsigned)b->nb, VH_TPB, 0, b->stream>>>(b->d_rowany, b->d_sliceany, b->d_colcount,
+                                                            b->R, b->C, b->Z, b->d_mt_crop);
+    VH_CHECK_LAUNCH();
+}
+
+struct MtArgs {
+    const MtStudy *st;
+    int32_t nb;
+    const float *proton;     // nullable: zeros (what the class substitutes for a missing proton)
+    const float *hp, *n4;
+    const uint8_t *mask, *def;
+    const int16_t *shell;    // nullable: the blank CI panel
+    const double *radii;
+    int64_t nbs;
+    double minvox;
+    const double *parula;
+    int64_t prow;
+    int64_t R, C, Z, V;
+    uint32_t *keys;          // [nb][6]
+    int32_t *flag;           // [nb]
+    uint8_t *img;
+};
+
+__global__ void k_mt_init(uint32_t *keys, int32_t *flag, int64_t nb) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nb) return;
+    for (int q = 0; q < 3; ++q) { keys[6 * v + 2 * q] = 0xffffffffu; keys[6 * v + 2 * q + 1] = 0u; }
+    flag[v] = 0;
+}
+
+// Crop minima / maxima of proton, HPvent and N4 of every study as sortable keys (order-free: integer
+// atomics).  blockIdx.y = study; its crop rows are dealt to the blocks of the column, a row's
+// [c][z] runs to the threads.
+__global__ __launch_bounds__(VH_TPB) void k_crop_minmax_b(MtArgs a) {
+    const int64_t b = blockIdx.y;
+    const MtStudy s = a.st[b];
+    if (s.nr == 0) return;
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    const int n = s.nc * s.ns;   // < 2^31 (check_dims)
+    for (int i = blockIdx.x; i < s.nr; i += gridDim.x) {
+        const int64_t base = b * a.V + ((int64_t)(s.r0 + i) * a.C + s.c0) * a.Z + s.s0;
+        for (int j = threadIdx.x; j < n; j += VH_TPB) {
+            const int c = j / s.ns, z = j - c * s.ns;
+            const int64_t idx = base + (int64_t)c * a.Z + z;
+            const uint32_t k0 = f2key(a.proton ? a.proton[idx] : 0.f);
+            const uint32_t k1 = f2key(a.hp[idx]), k2 = f2key(a.n4[idx]);
+            lo[0] = min(lo[0], k0); hi[0] = max(hi[0], k0);
+            lo[1] = min(lo[1], k1); hi[1] = max(hi[1], k1);
+            lo[2] = min(lo[2], k2); hi[2] = max(hi[2], k2);
+        }
+    }
+    __shared__ uint32_t s_k[6][VH_TPB / VH_WAVE];
+    for (int q = 0; q < 3; ++q) {
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[q] = min(lo[q], (uint32_t)__shfl_xor((int)lo[q], o));
+            hi[q] = max(hi[q], (uint32_t)__shfl_xor((int)hi[q], o));
+        }
+        if ((threadIdx.x & (VH_WAVE - 1)) == 0) {
+            s_k[2 * q][threadIdx.x / VH_WAVE] = lo[q];
+            s_k[2 * q + 1][threadIdx.x / VH_WAVE] = hi[q];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const bool mx = threadIdx.x & 1;
+        uint32_t v = s_k[threadIdx.x][0];
+        for (int w = 1; w < VH_TPB / VH_WAVE; ++w) v = mx ? max(v, s_k[threadIdx.x][w]) : min(v, s_k[threadIdx.x][w]);
+        if (mx) atomicMax(&a.keys[6 * b + threadIdx.x], v);
+        else atomicMin(&a.keys[6 * b + threadIdx.x], v);
+    }
+}
+
+// screenShot's normalize (:460-464) of a float32 array, then uint8(. * 255) with the product in
+// float64 (IMAGE is float64: the parula columns are)
+__device__ __forceinline__ uint8_t mt_u8(float x, float mn, float rng) {
+    const float v = rng != 0.f ? (x - mn) / rng : x;
+    return np_u8((double)v * 255.0);
+}
+
+// t / d and the remainder for small non-negative t (< 2^16) and 1 <= d <= 256 with inv = 1.f / d: a
+// float product and one correction step instead of an integer division per element
+__device__ __forceinline__ int mt_divmod(int t, int d, float inv, int &rem) {
+    int q = __float2int_rz(((float)t + 0.5f) * inv);
+    rem = t - q * d;
+    if (rem < 0) { --q; rem += d; }
+    else if (rem >= d) { ++q; rem -= d; }
+    return q;
+}
+
+// One workgroup = one crop row of one study, up to MT_COLS columns and MT_ZC slices of it.  It reads
+// the contiguous [c][z] runs of that row once (proton, HPvent, N4, defect, the shell, and the mask's
+// four neighbours for calculateBorder), composes the five drawn panels' RGB triples in LDS, one
+// [c][3] row per panel and slice, and writes every row out: the image is [panel nr + i][s nc + j][3],
+// so a row is a contiguous run of 3 ncw bytes (and consecutive slices follow each other when the
+// crop is one chunk wide).  A run goes out as aligned dwords -- the LDS words shifted to the run's
+// alignment -- with up to three head and tail bytes, whatever nc is; consecutive threads take
+// consecutive dwords of consecutive runs.  The two blank panels are written as zeros by the same loop.
+// LDS rows are padded to an odd number of words: the threads of a wave hold consecutive slices of a
+// column, and 3 ncw bytes is a multiple of 32 words' worth of banks for a full chunk.
+// The workgroup finds its study in the prefix MtStudy::wg0 (binary search; uniform, scalar loads).
+#define MT_RSW_MAX ((MT_COLS * 3 / 4) | 1)
+__global__ __launch_bounds__(VH_TPB) void k_montage_b(MtArgs a) {
+    __shared__ uint32_t sbuf[MT_DRAWN * MT_ZC * MT_RSW_MAX];
+    uint8_t *sb = reinterpret_cast<uint8_t *>(sbuf);
+    const int64_t w = blockIdx.x;
+    int b = 0, hi = a.nb;   // st[b].wg0 <= w < st[hi].wg0: the last such b is a study with workgroups
+    while (hi - b > 1) {
+        const int mid = (b + hi) >> 1;
+        if (a.st[mid].wg0 <= w) b = mid; else hi = mid;
+    }
+    const MtStudy s = a.st[b];
+    int64_t q = w - s.wg0;
+    const int cchunk = (int)(q % s.ncc);
+    q /= s.ncc;
+    const int zchunk = (int)(q % s.nzc), i = (int)(q / s.nzc);
+    const int j0 = cchunk * MT_COLS, z0 = zchunk * MT_ZC;
+    const int ncw = min(MT_COLS, s.nc - j0), nz = min(MT_ZC, s.ns - z0);
+    const int L = ncw * 3;                        // bytes of a row
+    const int rsw = ((L + 3) >> 2) | 1;           // its LDS stride in words (odd), <= MT_RSW_MAX
+    const int psz = MT_ZC * MT_RSW_MAX * 4;       // bytes of a panel in LDS
+    // offsets inside a volume are < 2^31 (check_dims): 32-bit index arithmetic
+    const int C = (int)a.C, Z = (int)a.Z;
+    const int r = s.r0 + i, rm = max(r - 1, 0), rp = min(r + 1, (int)a.R - 1);
+    const int64_t vb = (int64_t)b * a.V;
+    const float *pr = a.proton ? a.proton + vb : nullptr, *hp = a.hp + vb, *n4 = a.n4 + vb;
+    const uint8_t *m = a.mask + vb, *def = a.def + vb;
+    const int16_t *shell = a.shell ? a.shell + vb : nullptr;
+    const uint32_t *k = a.keys + 6 * b;
+    const float mnP = key2f(k[0]), rgP = key2f(k[1]) - mnP;   // np.max(x) - np.min(x), float32
+    const float mnH = key2f(k[2]), rgH = key2f(k[3]) - mnH;
+    const float mnN = key2f(k[4]), rgN = key2f(k[5]) - mnN;
+    const int n = ncw * nz;
+    const float inz = 1.f / (float)nz;
+    for (int j = threadIdx.x; j < n; j += VH_TPB) {
+        int z;
+        const int c = mt_divmod(j, nz, inz, z);
+        const int cc = s.c0 + j0 + c, zz = s.s0 + z0 + z;
+        const int cm = max(cc - 1, 0), cp = min(cc + 1, C - 1);
+        const int idx = (r * C + cc) * Z + zz;
+        const uint8_t p8 = mt_u8(pr ? pr[idx] : 0.f, mnP, rgP);
+        const uint8_t h8 = mt_u8(hp[idx], mnH, rgH);
+        const uint8_t n8 = mt_u8(n4[idx], mnN, rgN);
+        // calculateBorder(mask) != 0: np.gradient along rows or columns, one-sided at the edges
+        const bool bd = m[(rp * C + cc) * Z + zz] != m[(rm * C + cc) * Z + zz] ||
+                        m[(r * C + cp) * Z + zz] != m[(r * C + cm) * Z + zz];
+        const bool df = def[idx] != 0;
+        uint8_t c0 = n8, c1 = n8, c2 = n8;   // the CI panel: N4 where CI == 0
+        if (shell) {
+            const int32_t sh = shell[idx];
+            const double ci = sh >= 0 && sh < a.nbs ? a.radii[sh] * a.minvox : 0.0;   // k_ci_expand16's value
+            const double tt = ci * 64.0 / 40.0;
+            if (ci > 0.0) {
+                if (!(tt < 9.2e18) || (int64_t)tt >= a.prow) {   // IndexError (:482-484)
+                    atomicOr(&a.flag[b], 1);
+                    c0 = c1 = c2 = 0;
+                } else {
+                    const double *pp = a.parula + 3 * (int64_t)tt;
+                    c0 = np_u8(pp[0] * 255.0); c1 = np_u8(pp[1] * 255.0); c2 = np_u8(pp[2] * 255.0);
+                }
+            }
+        }
+        uint8_t *o = sb + z * rsw * 4 + c * 3;
+        o[0] = p8; o[1] = p8; o[2] = p8;
+        o += psz;
+        o[0] = h8; o[1] = h8; o[2] = h8;
+        o += psz;
+        o[0] = bd ? (uint8_t)0 : n8;            // N4*(~border) + {0, 1, 1}*border
+        o[1] = bd ? (uint8_t)255 : n8;
+        o[2] = bd ? (uint8_t)255 : n8;
+        o += psz;
+        o[0] = df ? (uint8_t)255 : n8;          // N4*(~defArr) + {defArr, 0, 0}
+        o[1] = df ? (uint8_t)0 : n8;
+        o[2] = df ? (uint8_t)0 : n8;
+        o += psz;
+        o[0] = c0; o[1] = c1; o[2] = c2;
+    }
+    __syncthreads();
+    // slot 0 of a run: its head and tail bytes; slots 1 ..: its aligned dwords
+    const int slots = (L >> 2) + 2;
+    const float islots = 1.f / (float)slots;
+    const int64_t nc3 = (int64_t)s.nc * 3;
+    const int64_t prow = (int64_t)s.nr * s.ns * nc3;                   // bytes of a panel
+    uint8_t *img = a.img + s.off + ((int64_t)i * s.ns + z0) * nc3 + j0 * 3;   // off is 4-byte aligned (VH_MT_ALIGN)
+    const int a0 = (int)((s.off + ((int64_t)i * s.ns + z0) * nc3 + j0 * 3) & 3);
+    for (int g = 0; g < 7; ++g) {
+        uint8_t *pg = img + g * prow;
+        const int ag = (a0 + (int)((g * prow) & 3)) & 3;
+        const int lp = g >= 2 ? (g - 2) * psz : 0;                     // the panel in LDS (read for g >= 2 only)
+        const uint8_t *sp = sb + lp;
+        for (int t = threadIdx.x; t < nz * slots; t += VH_TPB) {
+            int d;
+            const int zr = mt_divmod(t, slots, islots, d);
+            const int64_t A = zr * nc3;                                // the run's start from pg
+            const int h = min((4 - ((ag + (int)(A & 3)) & 3)) & 3, L); // head bytes up to the first aligned dword
+            const int nd = (L - h) >> 2;                               // aligned dwords
+            const int S = zr * rsw * 4;                                // the run in the panel's LDS
+            if (d == 0) {
+                const int tail = L - h - 4 * nd;                       // < 4
+                for (int e = 0; e < h; ++e) pg[A + e] = g >= 2 ? sp[S + e] : (uint8_t)0;
+                for (int e = L - tail; e < L; ++e) pg[A + e] = g >= 2 ? sp[S + e] : (uint8_t)0;
+            } else if (d <= nd) {
+                uint32_t v = 0u;
+                if (g >= 2) {
+                    const int bb = S + h + 4 * (d - 1), wi = (lp + bb) >> 2, sh = (bb & 3) * 8;
+                    v = sbuf[wi];
+                    if (sh) v = (v >> sh) | (sbuf[wi + 1] << (32 - sh));   // word wi + 1 starts inside the row
+                }
+                *reinterpret_cast<uint32_t *>(pg + A + h + 4 * (d - 1)) = v;
+            }
+        }
+    }
+}
+
+void vh_montage_b_launch(vh_batch *b, bool proton, int64_t prow, bool ci_on) {
+    hipStream_t st = b->stream;
+    MtArgs a{};
+    a.st = b->d_mt_st; a.nb = (int32_t)b->nb;
+    a.proton = proton ? b->d_proton : nullptr;
+    a.hp = b->d_hp; a.n4 = b->d_n4_last;
+    a.mask = b->d_mask; a.def = b->d_defect;
+    a.shell = ci_on ? b->d_ci_shell16 : nullptr;
+    a.radii = b->d_ci_radii; a.nbs = b->ci_nbs; a.minvox = b->ci_minvox;
+    a.parula = b->d_mt_parula; a.prow = prow;
+    a.R = b->R; a.C = b->C; a.Z = b->Z; a.V = b->V;
+    a.keys = b->d_mt_keys; a.flag = b->d_mt_flag; a.img = b->d_mt_img;
+    int64_t vox = 0;
+    for (int64_t i = 0; i < b->nb; ++i) vox += (int64_t)b->mt_st[i].nr * b->mt_st[i].nc * b->mt_st[i].ns;
+    const int64_t grid = b->mt_st[b->nb].wg0;
+    // per crop voxel: the min/max pass (hp, N4, proton), then hp, N4, proton, defect, mask (its
+    // neighbours come from the caches), the shell, and 21 bytes out
+    const double per = (proton ? 12.0 : 8.0) * 2.0 + 2.0 + (ci_on ? 2.0 : 0.0) + 21.0;
+    ScopedKTimer tm(b, "montage_b", per * (double)vox);
+    k_mt_init<<<(unsigned)((b->nb + VH_TPB - 1) / VH_TPB), VH_TPB, 0, st>>>(a.keys, a.flag, b->nb);
+    VH_CHECK_LAUNCH();
+    if (grid == 0) return;   // every study empty
+    const unsigned rows = (unsigned)std::min<int64_t>(b->R, 64);
+    k_crop_minmax_b<<<dim3(rows, (unsigned)b->nb), VH_TPB, 0, st>>>(a);
+    VH_CHECK_LAUNCH();
+    k_montage_b<<<(unsigned)grid, VH_TPB, 0, st>>>(a);
+    VH_CHECK_LAUNCH();
+}

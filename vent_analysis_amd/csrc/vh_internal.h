@@ -189,6 +189,19 @@ struct vh_pipe {
     std::atomic<int64_t> pinned{0}, pinned_peak{0}, staged_spans{0};
 };
 
+// One study of the batch montage (vh_batch_montage_layout): its crop, how its crop rows split into
+// workgroups of k_montage_b, where its image starts in the compact buffer and its first workgroup.
+// Entry nb of the array closes the prefix: off = the buffer's size, wg0 = the grid.
+struct MtStudy {
+    int32_t r0, nr, c0, nc, s0, ns;
+    int32_t ncc, nzc;        // column / slice chunks of a crop row (MT_COLS x MT_ZC voxels each)
+    int64_t off;             // byte at which the study's image starts (a multiple of VH_MT_ALIGN)
+    int64_t wg0;             // first workgroup of the study; an empty study has none
+};
+#define VH_MT_ALIGN 64
+#define VH_MT_COLS 64        // crop columns per workgroup of k_montage_b
+#define VH_MT_ZC 32          // crop slices per workgroup
+
 struct vh_batch {
     vh_ctx *ctx = nullptr;
     hipStream_t stream = nullptr;    // every launch and copy of this batch (batches overlap)
@@ -290,6 +303,24 @@ struct vh_batch {
     double ci_minvox = 0.0;
     bool have_defect = false;        // vh_batch_set_defect uploaded the defect maps
     bool have_ci = false;            // vh_batch_ci has been enqueued
+    // vh_batch_overlay / vh_batch_montage (export.hip): every buffer on first demand
+    bool ci_fresh = false;           // vh_batch_ci was enqueued after the last change of the resident defect maps
+    uint8_t *d_ov_rgb = nullptr;     // [nb][Z][R][C][3] the overlay frames
+    uint32_t *d_ov_mm = nullptr;     // [nb][2] min / max of |N4| (float bits)
+    bool ov_valid = false;           // vh_batch_overlay has been enqueued since the last run
+    float *d_proton = nullptr;       // [nb][V] the montage's proton volumes
+    int32_t *d_mt_crop = nullptr;    // [nb][8] k_crop_layout: r0, nr, c0, nc, s0, ns, status, 0
+    MtStudy *d_mt_st = nullptr;      // [nb + 1]
+    uint32_t *d_mt_keys = nullptr;   // [nb][6] crop min / max keys of proton, HPvent, N4
+    int32_t *d_mt_flag = nullptr;    // [nb] 1: a CI colour index reached prow
+    double *d_mt_parula = nullptr;   // [mt_prow_cap][3]
+    int64_t mt_prow_cap = 0;
+    uint8_t *d_mt_img = nullptr;     // the compact image buffer, mt_img_cap bytes
+    int64_t mt_img_cap = 0;
+    std::vector<MtStudy> mt_st;      // host copy of d_mt_st (valid while mt_layout_valid)
+    std::vector<int32_t> mt_status;  // [nb] VH_OK / VH_ERR_EMPTY of the layout
+    bool mt_layout_valid = false;    // the layout is the last run's
+    bool mt_valid = false;           // vh_batch_montage has been enqueued since the last run
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -449,6 +480,9 @@ __device__ inline void snr_block_write(double (&acc)[4], double (*s_red)[VH_TPB 
 // export.hip (rendering after the hot path)
 void vh_overlay_launch(hipStream_t s, const float *d_n4, const uint8_t *d_def, int64_t R, int64_t C,
                        int64_t Z, int64_t nb, uint32_t *d_mm, uint8_t *d_rgb);
+// the batch renderings (vh_batch_overlay is vh_overlay_launch on the resident buffers)
+void vh_crop_layout_launch(vh_batch *b);   // -> d_mt_crop, from the last run's mask statistics
+void vh_montage_b_launch(vh_batch *b, bool proton, int64_t prow, bool ci_on);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
