@@ -55,7 +55,7 @@ def test_null_batch_is_an_argument_error():
     ((19, 70, 5), BR.wide, (0, 19, 0, 70, 1, 3)),          # 64 + 6 columns
     ((24, 20, 70), BR.ellipse, (0, 24, 0, 20, 1, 68)),     # 32 + 32 + 4 slices
     ((128, 128, 24), BR.ellipse, (21, 87, 27, 75, 1, 22)),  # 64 + 11 columns
-], ids=str)
+], ids=lambda v: getattr(v, "__name__", None) or "_".join(map(str, v)))   # no address in an id
 def test_reference_crops(shape, mask, crop):
     """Drift in the inputs of the GPU cases is noticed."""
     assert BR.crop6(mask(shape)) == crop

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from vent_analysis_amd import _lib
+from vent_analysis_amd.synth import synth_batch
 
 import batch_render_ref as BR
 
@@ -171,3 +172,38 @@ def test_deterministic_and_leaves_the_run_state():
     for x, y in zip(before, after):
         assert np.array_equal(x, y, equal_nan=True)
     B.close()
+
+
+def test_montage_buffer_grows_on_one_batch():
+    """One batch is run and montaged twice; the second upload's masks give larger crops, so the
+    compact image buffer is freed and allocated again.  The second montage equals a fresh batch's
+    byte for byte (layout, status and every image)."""
+    hp, _ = synth_batch(40, 36, 9, 2, base_seed=41)
+    small = np.zeros(hp.shape, np.uint8)
+    small[0, 16:22, 15:20, 3:6] = 1
+    small[1, 10:15, 20:24, 4:5] = 1
+    large = np.zeros(hp.shape, np.uint8)
+    large[0, 4:36, 3:33, 0:9] = 1
+    large[1, 8:30, 6:31, 1:8] = 1
+    B = run_batch(hp, small)
+    try:
+        off_small = B.montage_layout()[1]
+        first, st1 = B.montage(PAL)
+        assert np.all(st1 == BR.VH_OK) and all(im is not None for im in first)
+        B.upload(hp, large)
+        B.run(B.options(vox=BR.VOX, do_n4=False))
+        crop, off, status = B.montage_layout()
+        assert off[-1] > off_small[-1]
+        got = [im.copy() for im in B.montage(PAL)[0]]
+    finally:
+        B.close()
+    F = run_batch(hp, large)
+    try:
+        fcrop, foff, fstatus = F.montage_layout()
+        fresh, fst = F.montage(PAL)
+        assert np.array_equal(crop, fcrop) and np.array_equal(off, foff) and np.array_equal(status, fstatus)
+        assert np.all(fst == BR.VH_OK)
+        for q in range(2):
+            assert got[q].shape == fresh[q].shape and got[q].tobytes() == fresh[q].tobytes(), q
+    finally:
+        F.close()

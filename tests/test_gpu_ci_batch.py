@@ -248,3 +248,23 @@ def test_batch_ci_argument_errors():
     _, sc, st = B.download_ci(maps=None)
     assert st[0] == _lib.VH_ERR_EMPTY and np.isnan(sc[0])
     B.close()
+
+
+def test_ci_workspace_grows_on_one_batch():
+    """One resident batch, the same maps under a table of few shells (Rmax 12) and then one of more
+    (Rmax 50): the shell histograms and the batch's copy of the radii are freed and allocated again.
+    Scalars, status and the int16 map equal those of a fresh batch given only the second table."""
+    shape = (40, 36, 9)
+    ds = np.stack([blobs(shape, 31), blobs(shape, 32, n=3)])
+    B = _lib.Batch(*shape, 2)
+    try:
+        small, radii_small = batch_ci(ds, 12, B=B)
+        got, radii = batch_ci(ds, 50, B=B)
+    finally:
+        B.close()
+    assert len(radii) > len(radii_small)
+    fresh, radii_f = batch_ci(ds, 50)
+    assert radii_f is radii
+    for a, b in zip(fresh, got):
+        assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
+    assert np.all(got[2] == _lib.VH_OK)

@@ -1211,3 +1211,46 @@ def test_n4_studies_smaller_than_the_pc_block_count(driver, nb):
     assert_n4_matches(n4[0], res[0].n4_iters[:4], res[0].n4_conv[:4], ref, its, conv, 0, ("tiny", driver))
     if nb == 2:
         assert np.array_equal(n4[1], hp[1])
+
+
+# ---- one batch across a change of the N4 workspace ---------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _regrow_case():
+    return synth_batch(37, 45, 7, 2, base_seed=11)
+
+
+@functools.lru_cache(maxsize=None)
+def _regrow_ref(b, max_iters, conv_mode):
+    hp, mk = _regrow_case()
+    return native.n4(hp[b], mk[b], max_iters=max_iters, conv_mode=conv_mode)
+
+
+@pytest.mark.parametrize("conv_mode", [0, 1])
+@pytest.mark.parametrize("mode,nb", [("sweep", 2), ("study", 2), ("grid", 1)])
+def test_n4_workspace_regrows_on_one_batch(mode, nb, conv_mode):
+    """One Batch runs N4 with 2, then 4, then 2 levels: the final lattice goes 5^3 -> 11^3 -> 5^3, so
+    the lattice buffers (and T, P1) are freed and allocated again once, and the third run uses them
+    with per-study strides larger than it needs.  Every run equals the oracle and, bit for bit, the
+    same run on a fresh Batch."""
+    hp, mk = (a[:nb] for a in _regrow_case())
+    fresh = {}
+    B = _lib.Batch(37, 45, 7, nb)
+    try:
+        B.upload(hp, mk)
+        for run, iters in enumerate(((4, 4), (4, 4, 4, 4), (4, 4))):
+            nl = len(iters)
+            B.run(B.options(do_n4=True, vox=(1.5, 1.5, 10.0), n4_mode=mode, max_iters=iters, conv_mode=conv_mode))
+            n4, _, _, _, res = B.download(n4=True)
+            if iters not in fresh:
+                fresh[iters] = _run_batch(hp, mk, mode, max_iters=iters, conv_mode=conv_mode)
+            f4, _, _, _, fres = fresh[iters]
+            for b in range(nb):
+                ref, its_ref, conv_ref = _regrow_ref(b, iters, conv_mode)
+                assert_n4_matches(n4[b], res[b].n4_iters[:nl], res[b].n4_conv[:nl], ref, its_ref, conv_ref,
+                                  conv_mode, (mode, run, b))
+                assert n4[b].tobytes() == f4[b].tobytes(), (mode, run, b)
+                assert list(res[b].n4_iters[:nl]) == list(fres[b].n4_iters[:nl]), (mode, run, b)
+                assert (np.array(res[b].n4_conv[:nl], np.float32).tobytes()
+                        == np.array(fres[b].n4_conv[:nl], np.float32).tobytes()), (mode, run, b)
+    finally:
+        B.close()

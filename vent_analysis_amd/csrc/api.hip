@@ -34,10 +34,7 @@ ScopedKTimer::ScopedKTimer(vh_batch *bb, const char *name, double bytes, bool st
     t = &b->timers[name];
     if (bytes > 0) t->bytes_per_launch = bytes;
     if (stamped) {
-        if (!b->d_kst) {
-            HIP_TRY(hipMalloc((void **)&b->d_kst, sizeof(unsigned long long) * 2 * VH_KST_CAP));
-            kst_reset(b);
-        }
+        if (b->d_kst.reserve(2 * VH_KST_CAP)) kst_reset(b);
         if (b->kst_n < VH_KST_CAP) {
             const int s = b->kst_n++;
             t->slots.push_back(s);
@@ -123,14 +120,21 @@ static int fail(vh_ctx *c, int code, const std::string &msg) {
     }                                                                                        \
     return VH_OK;
 
-template <typename T>
-static void dalloc(T **p, size_t n) {
-    HIP_TRY(hipMalloc((void **)p, sizeof(T) * (n ? n : 1)));
+// Buf's allocator (devbuf.h): the library's only device and pinned-host allocations, but for
+// vh_host_alloc / vh_host_free, whose memory the caller owns
+void *vh_mem_alloc(int kind, size_t bytes) {
+    void *p = nullptr;
+    if (kind == 0)
+        HIP_TRY(hipMalloc(&p, bytes));
+    else
+        HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    return p;
 }
-template <typename T>
-static void dfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+void vh_mem_free(int kind, void *p) {
+    if (kind == 0)
+        (void)hipFree(p);
+    else
+        (void)hipHostFree(p);
 }
 
 static void check_dims(int64_t R, int64_t C, int64_t Z, int64_t batch) {
@@ -144,31 +148,15 @@ static void check_dims(int64_t R, int64_t C, int64_t Z, int64_t batch) {
 
 static void batch_free(vh_batch *b) {
     if (!b) return;
+    b->kst_n = 0;   // no stamp reset: nothing is enqueued on the drained stream
     clear_timers(b);
-    dfree(b->d_kst);
-    dfree(b->d_hp); dfree(b->d_mask); dfree(b->d_n4);
-    dfree(b->d_defect); dfree(b->d_border); dfree(b->d_lb); dfree(b->d_km);
-    dfree(b->d_colrange); dfree(b->d_colcount); dfree(b->d_colstart); dfree(b->d_colbits); dfree(b->d_colbnz); dfree(b->d_snrpart);
-    dfree(b->d_rowany); dfree(b->d_colany); dfree(b->d_sliceany);
-    dfree(b->d_sc); dfree(b->d_part); dfree(b->d_keys0); dfree(b->d_keys1); dfree(b->d_tilecnt);
-    dfree(b->d_cohort);
-    dfree(b->d_L0); dfree(b->d_lat); dfree(b->d_E);
-    dfree(b->d_numfix); dfree(b->d_rowstart); dfree(b->d_rowmask); dfree(b->d_rrank); dfree(b->d_iscan); dfree(b->d_D); dfree(b->d_perm); dfree(b->d_P1); dfree(b->d_den); dfree(b->d_T); dfree(b->d_pcdrift);
-    dfree(b->d_U); dfree(b->d_ridx); dfree(b->d_cp); dfree(b->d_cvol); dfree(b->d_hpart); dfree(b->d_hred); dfree(b->d_cpart); dfree(b->d_st); dfree(b->d_nactive); dfree(b->d_tabs); dfree(b->d_twiddle); dfree(b->d_study_lv); dfree(b->d_study_order); dfree(b->d_pcg); dfree(b->d_stg); dfree(b->d_sortg); dfree(b->d_study_latg);
-    dfree(b->d_bitmap); dfree(b->d_ci_list); dfree(b->d_ci_shell); dfree(b->d_ci_hist);
-    dfree(b->d_ci_status);
-    dfree(b->d_ci_count); dfree(b->d_ci_map);
-    dfree(b->d_ci_shell16); dfree(b->d_ci_next); dfree(b->d_ci_radii);
-    dfree(b->d_ov_rgb); dfree(b->d_ov_mm); dfree(b->d_proton); dfree(b->d_mt_crop); dfree(b->d_mt_st);
-    dfree(b->d_mt_keys); dfree(b->d_mt_flag); dfree(b->d_mt_parula); dfree(b->d_mt_img);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     if (b->st_n4) (void)hipStreamDestroy(b->st_n4);
     if (b->ev_n4_pre) (void)hipEventDestroy(b->ev_n4_pre);
     if (b->ev_n4_post) (void)hipEventDestroy(b->ev_n4_post);
     if (b->ev_cpre) (void)hipEventDestroy(b->ev_cpre);
     if (b->ev_cpost) (void)hipEventDestroy(b->ev_cpost);
-    if (b->h_flags) (void)hipHostFree(b->h_flags);
-    delete b;
+    delete b;   // the buffers (every caller has drained the batch's stream)
 }
 
 static vh_batch *batch_new(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t nb) {
@@ -219,33 +207,33 @@ static vh_batch *batch_new(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t
     b->max_tiles = (b->V + VH_SORT_TILE - 1) / VH_SORT_TILE;
     const size_t NV = (size_t)nb * b->V;
     try {
-        dalloc(&b->d_hp, NV);
-        dalloc(&b->d_mask, NV);
-        dalloc(&b->d_n4, NV);
-        dalloc(&b->d_defect, NV);
-        dalloc(&b->d_border, NV);
-        dalloc(&b->d_lb, NV);
-        dalloc(&b->d_colrange, (size_t)nb * b->CZ * 2);
-        dalloc(&b->d_colcount, (size_t)nb * b->CZ);
-        dalloc(&b->d_colbits, (size_t)nb * ((R + 31) / 32) * b->CZ);
-        dalloc(&b->d_colbnz, (size_t)nb * ((R + 31) / 32) * b->CZ);
-        dalloc(&b->d_colstart, (size_t)nb * b->CZ);
-        dalloc(&b->d_rowany, (size_t)nb * R);
-        dalloc(&b->d_colany, (size_t)nb * C);
-        dalloc(&b->d_sliceany, (size_t)nb * Z);
-        dalloc(&b->d_sc, (size_t)nb);
+        b->d_hp.reserve(NV);
+        b->d_mask.reserve(NV);
+        b->d_n4.reserve(NV);
+        b->d_defect.reserve(NV);
+        b->d_border.reserve(NV);
+        b->d_lb.reserve(NV);
+        b->d_colrange.reserve((size_t)nb * b->CZ * 2);
+        b->d_colcount.reserve((size_t)nb * b->CZ);
+        b->d_colbits.reserve((size_t)nb * ((R + 31) / 32) * b->CZ);
+        b->d_colbnz.reserve((size_t)nb * ((R + 31) / 32) * b->CZ);
+        b->d_colstart.reserve((size_t)nb * b->CZ);
+        b->d_rowany.reserve((size_t)nb * R);
+        b->d_colany.reserve((size_t)nb * C);
+        b->d_sliceany.reserve((size_t)nb * Z);
+        b->d_sc.reserve((size_t)nb);
         b->part_blocks = (b->CZ + VH_TPB - 1) / VH_TPB;
         b->slab_blocks = b->part_blocks * ((R + VH_SLAB - 1) / VH_SLAB);
-        dalloc(&b->d_snrpart, (size_t)nb * b->slab_blocks * 4);
+        b->d_snrpart.reserve((size_t)nb * b->slab_blocks * 4);
         const int64_t max_chunks = (b->V + 8191) / 8192;
         const int64_t eval_slots = ((b->CZ + 63) / 64) * ((R + 15) / 16);   // n4 eval partial slots
-        dalloc(&b->d_part, (size_t)nb * std::max<int64_t>(std::max<int64_t>(b->part_blocks * 4, max_chunks),
+        b->d_part.reserve((size_t)nb * std::max<int64_t>(std::max<int64_t>(b->part_blocks * 4, max_chunks),
                                                          eval_slots * 2));
-        dalloc(&b->d_keys0, NV);
-        dalloc(&b->d_keys1, NV);
-        dalloc(&b->d_tilecnt, (size_t)nb * 256 * b->max_tiles);
-        dalloc(&b->d_cohort, (size_t)VH_COHORT_BINS);
-        HIP_TRY(hipMemset(b->d_cohort, 0, sizeof(uint64_t) * VH_COHORT_BINS));
+        b->d_keys0.reserve(NV);
+        b->d_keys1.reserve(NV);
+        b->d_tilecnt.reserve((size_t)nb * 256 * b->max_tiles);
+        if (b->d_cohort.reserve((size_t)VH_COHORT_BINS))
+            HIP_TRY(hipMemset(b->d_cohort, 0, sizeof(uint64_t) * VH_COHORT_BINS));
     } catch (...) {
         batch_free(b);
         throw;
@@ -380,17 +368,11 @@ static void pipe_free(vh_pipe *p) {
             (void)hipStreamSynchronize(q.b->stream);
             batch_free(q.b);
         }
-        if (q.hp) (void)hipHostFree(q.hp);
-        if (q.d_pack) (void)hipFree(q.d_pack);
-        if (q.mb) (void)hipHostFree(q.mb);
-        if (q.n4) (void)hipHostFree(q.n4);
-        if (q.u8) (void)hipHostFree(q.u8);
         if (q.done) (void)hipEventDestroy(q.done);
         if (q.h2d) (void)hipEventDestroy(q.h2d);
         if (q.packed) (void)hipEventDestroy(q.packed);
-
     }
-    delete p;
+    delete p;   // the slots' staging buffers
 }
 
 // The context's cached scratch batch for the host-buffer entry points (caller holds ctx->mu).
@@ -483,11 +465,9 @@ int vh_destroy(vh_ctx *ctx) {
         ctx->scratch = nullptr;
     }
     if (ctx->comm) ncclCommDestroy((ncclComm_t)ctx->comm);
-    if (ctx->h_ci_sc) (void)hipHostFree(ctx->h_ci_sc);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
     if (ctx->comm_st) (void)hipStreamDestroy(ctx->comm_st);
-    if (ctx->recon_buf) (void)hipFree(ctx->recon_buf);
-    delete ctx;
+    delete ctx;   // recon_buf, h_ci_sc
     return VH_OK;
 }
 
@@ -634,18 +614,12 @@ static void ci_host(vh_ctx *ctx, const uint8_t *defect, int64_t R, int64_t C, in
     // stores cross the link; no device map, no copy), else a device map and one D2H
     double *d_map = ci_array ? (double *)host_mapped(ci_array, sizeof(double) * NV) : nullptr;
     if (ci_array && !d_map) {
-        if (!b->d_ci_map) HIP_TRY(hipMalloc(&b->d_ci_map, sizeof(double) * NV));
+        b->d_ci_map.reserve(NV);
         d_map = b->d_ci_map;
     }
     // the scalars likewise, into the context's device-mapped page-locked array (a small D2H runs as
     // a blit kernel, r4al: 4.7 us plus its gap)
-    if (ctx->h_ci_sc_cap < batch) {
-        if (ctx->h_ci_sc) HIP_TRY(hipHostFree(ctx->h_ci_sc));
-        ctx->h_ci_sc = nullptr;
-        ctx->h_ci_sc_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_ci_sc, sizeof(VolScalars) * batch, hipHostMallocDefault));
-        ctx->h_ci_sc_cap = batch;
-    }
+    ctx->h_ci_sc.reserve((size_t)batch);
     VolScalars *d_hsc = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void **)&d_hsc, ctx->h_ci_sc, 0));
     vh_ci_run(b, t, minvox, d_map, d_hsc);
@@ -771,12 +745,7 @@ int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox) {
         if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         try {
             vh_ci_run(b, t, minvox, nullptr, nullptr, vh_ci_batch_form(b));
-            if (t->nbs > b->ci_radii_cap) {
-                dfree(b->d_ci_radii);
-                b->ci_radii_cap = 0;
-                dalloc(&b->d_ci_radii, (size_t)t->nbs);
-                b->ci_radii_cap = t->nbs;
-            }
+            b->d_ci_radii.reserve((size_t)t->nbs);
             HIP_TRY(hipMemcpyAsync(b->d_ci_radii, t->d_radii, sizeof(double) * t->nbs, hipMemcpyDeviceToDevice,
                                    b->stream));
         } catch (...) {   // whatever was launched before the failure still reads the table
@@ -828,7 +797,7 @@ static void batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border,
     const size_t NV = (size_t)b->nb * b->V;
     hipStream_t st = b->stream;
     if (km && !b->km_valid) {
-        if (!b->d_km) dalloc(&b->d_km, NV);
+        b->d_km.reserve(NV);
         vh_launch_km_labels(b, b->d_n4_last, b->d_km);
         b->km_valid = true;
     }
@@ -920,7 +889,7 @@ int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *
         HIP_TRY(hipSetDevice(b->ctx->device));
         const size_t NV = (size_t)b->nb * b->V;
         if (ci_array) {
-            if (!b->d_ci_map) HIP_TRY(hipMalloc(&b->d_ci_map, sizeof(double) * NV));
+            b->d_ci_map.reserve(NV);
             vh_ci_expand(b, b->d_ci_map);
             HIP_TRY(hipMemcpyAsync(ci_array, b->d_ci_map, sizeof(double) * NV, hipMemcpyDeviceToHost, b->stream));
         }
@@ -1038,8 +1007,8 @@ int vh_overlay(vh_ctx *ctx, const float *n4, const uint8_t *defect, int64_t R, i
         HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
         HIP_TRY(hipMemcpyAsync(b->d_defect, defect, NV, hipMemcpyHostToDevice, b->stream));
         // rgb (3 B/voxel) in the sort-key buffer (4 B/voxel), the |x| min/max in the partials
-        uint8_t *d_rgb = reinterpret_cast<uint8_t *>(b->d_keys0);
-        uint32_t *d_mm = reinterpret_cast<uint32_t *>(b->d_part);
+        uint8_t *d_rgb = reinterpret_cast<uint8_t *>(b->d_keys0.get());
+        uint32_t *d_mm = reinterpret_cast<uint32_t *>(b->d_part.get());
         vh_overlay_launch(b->stream, b->d_n4, b->d_defect, R, C, Z, batch, d_mm, d_rgb);
         HIP_TRY(hipMemcpyAsync(rgb, d_rgb, 3 * NV, hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1074,8 +1043,8 @@ int vh_batch_overlay(vh_batch *b) {
         if (b->nb > 65535 || b->R > 65535) throw VhError{VH_ERR_ARG, "overlay: batch or rows out of range"};
         HIP_TRY(hipSetDevice(b->ctx->device));
         const size_t NV = (size_t)b->nb * b->V;
-        if (!b->d_ov_rgb) dalloc(&b->d_ov_rgb, 3 * NV);
-        if (!b->d_ov_mm) dalloc(&b->d_ov_mm, 2 * (size_t)b->nb);
+        b->d_ov_rgb.reserve(3 * NV);
+        b->d_ov_mm.reserve(2 * (size_t)b->nb);
         // N4 twice (min/max, then the frames), the defect map, 3 bytes out
         ScopedKTimer tm(b, "overlay_b", 12.0 * (double)NV);
         vh_overlay_launch(b->stream, b->d_n4_last, b->d_defect, b->R, b->C, b->Z, b->nb, b->d_ov_mm, b->d_ov_rgb);
@@ -1100,8 +1069,8 @@ static void batch_montage_layout(vh_batch *b) {
     if (b->mt_layout_valid) return;
     HIP_TRY(hipSetDevice(b->ctx->device));
     const int64_t nb = b->nb;
-    if (!b->d_mt_crop) dalloc(&b->d_mt_crop, (size_t)nb * 8);
-    if (!b->d_mt_st) dalloc(&b->d_mt_st, (size_t)nb + 1);
+    b->d_mt_crop.reserve((size_t)nb * 8);
+    b->d_mt_st.reserve((size_t)nb + 1);
     vh_crop_layout_launch(b);
     std::vector<int32_t> h((size_t)nb * 8);
     d2h_on_stream(b, h.data(), b->d_mt_crop, sizeof(int32_t) * h.size());
@@ -1157,22 +1126,14 @@ int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int
         HIP_TRY(hipSetDevice(b->ctx->device));
         const size_t NV = (size_t)b->nb * b->V;
         const int64_t total = b->mt_st[b->nb].off;
-        if (!b->d_mt_keys) dalloc(&b->d_mt_keys, 6 * (size_t)b->nb);
-        if (!b->d_mt_flag) dalloc(&b->d_mt_flag, (size_t)b->nb);
-        if (prow > b->mt_prow_cap) {
-            dfree(b->d_mt_parula);
-            b->mt_prow_cap = 0;
-            dalloc(&b->d_mt_parula, 3 * (size_t)prow);
-            b->mt_prow_cap = prow;
-        }
-        if (total > b->mt_img_cap) {
+        b->d_mt_keys.reserve(6 * (size_t)b->nb);
+        b->d_mt_flag.reserve((size_t)b->nb);
+        b->d_mt_parula.reserve(3 * (size_t)prow);
+        if ((size_t)total > b->d_mt_img.size()) {
             HIP_TRY(hipStreamSynchronize(b->stream));   // an earlier montage may still be writing
-            dfree(b->d_mt_img);
-            b->mt_img_cap = 0;
-            dalloc(&b->d_mt_img, (size_t)total);
-            b->mt_img_cap = total;
+            b->d_mt_img.reserve((size_t)total);
         }
-        if (proton && !b->d_proton) dalloc(&b->d_proton, NV);
+        if (proton) b->d_proton.reserve(NV);
         HIP_TRY(hipMemcpyAsync(b->d_mt_parula, parula, sizeof(double) * 3 * prow, hipMemcpyHostToDevice, b->stream));
         if (proton) HIP_TRY(hipMemcpyAsync(b->d_proton, proton, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
         vh_montage_b_launch(b, proton != nullptr, prow, b->ci_fresh);
@@ -1206,14 +1167,8 @@ int vh_recon(vh_ctx *ctx, const double *k, int64_t n0, int64_t n1, int64_t nz, d
         HIP_TRY(hipSetDevice(ctx->device));
         if (!ctx->aux) HIP_TRY(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
         const size_t NV = (size_t)(n0 * n1 * nz), bytes = sizeof(double2) * (3 * NV + n0 + n1);
-        if (bytes > ctx->recon_cap) {
-            if (ctx->recon_buf) HIP_TRY(hipFree(ctx->recon_buf));
-            ctx->recon_buf = nullptr;
-            ctx->recon_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->recon_buf, bytes));
-            ctx->recon_cap = bytes;
-        }
-        double2 *d_in = (double2 *)ctx->recon_buf, *d_tmp = d_in + NV, *d_out = d_tmp + NV,
+        ctx->recon_buf.reserve(bytes);
+        double2 *d_in = (double2 *)ctx->recon_buf.get(), *d_tmp = d_in + NV, *d_out = d_tmp + NV,
                 *d_tw0 = d_out + NV, *d_tw1 = d_tw0 + n0;
         hipStream_t st = ctx->aux;
         HIP_TRY(hipMemcpyAsync(d_in, k, sizeof(double2) * NV, hipMemcpyHostToDevice, st));
@@ -1389,21 +1344,21 @@ int vh_pipe_create(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t sub, in
                 p->slot.emplace_back();
                 vh_pipe::Slot &q = p->slot.back();
                 q.b = batch_new(ctx, R, C, Z, sub);
-                HIP_TRY(hipHostMalloc((void **)&q.hp, sizeof(float) * NV));
-                HIP_TRY(hipHostMalloc((void **)&q.n4, sizeof(float) * NV));
+                q.hp.reserve(NV);
+                q.n4.reserve(NV);
                 // the chunk's outputs leave the GPU as ONE copy: the per-study scalars and N4 states,
                 // then the packed maps.  Small copies (the scalars were two of ~20 / 11 KiB) run as
                 // blit kernels (__amd_rocclr_copyBuffer), which wait for a CU like any kernel -- for
                 // milliseconds while k_n4_study holds every CU's LDS (r4a trace); one large copy
                 // goes to the SDMA engines.
                 q.scal = (sizeof(VolScalars) * sub + sizeof(N4State) * sub + 4095) / 4096 * 4096;
-                HIP_TRY(hipHostMalloc((void **)&q.u8, 2 * NV + q.scal));   // mask in | scalars + maps out
+                q.u8.reserve(2 * NV + q.scal);   // mask in | scalars + maps out
                 HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&q.h2d, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&q.packed, hipEventDisableTiming));
-                HIP_TRY(hipMalloc((void **)&q.d_pack, (size_t)NV + q.scal));
+                q.d_pack.reserve((size_t)NV + q.scal);
                 q.mb_half = ((size_t)NV / 8 + 1 + 63) / 64 * 64;
-                HIP_TRY(hipHostMalloc((void **)&q.mb, 2 * q.mb_half));
+                q.mb.reserve(2 * q.mb_half);
                 q.sc = reinterpret_cast<VolScalars *>(q.u8 + NV);
                 q.st = reinterpret_cast<N4State *>(q.u8 + NV + sizeof(VolScalars) * sub);
                 q.res.resize(sub);
@@ -1674,9 +1629,9 @@ int vh_pipe_run(vh_pipe *p, const float *hp, const uint8_t *mask, int64_t n, con
                 if (h2d_order == 2 && c.k > 0) HIP_TRY(hipEventSynchronize(p->slot[(c.k - 1) % slots].h2d));
                 // the copies first (the event marks their end: the next chunk's H2D waits for it
                 // on the host), then the kernels that consume them
-                c.sp[0].h2d((char *)b->d_hp, (char *)q.hp, b->stream);
+                c.sp[0].h2d((char *)b->d_hp.get(), (char *)q.hp.get(), b->stream);
                 if (c.mbits) HIP_TRY(hipMemcpyAsync(q.d_pack, c.mb, (CV + 7) / 8, hipMemcpyHostToDevice, b->stream));
-                else c.sp[1].h2d((char *)b->d_mask, (char *)qm, b->stream);
+                else c.sp[1].h2d((char *)b->d_mask.get(), (char *)qm, b->stream);
                 HIP_TRY(hipEventRecord(q.h2d, b->stream));
                 if (c.mbits) {
                     k_unpack_mask<<<(unsigned)std::min<int64_t>(4096, ((int64_t)(CV + 7) / 8 + 255) / 256), 256, 0,
@@ -1707,9 +1662,9 @@ int vh_pipe_run(vh_pipe *p, const float *hp, const uint8_t *mask, int64_t n, con
                     const int64_t stw = opts->do_n4 ? (int64_t)(sizeof(N4State) * sub / 4) : 0;
                     k_pack_maps<<<(unsigned)std::min<int64_t>(4096, (cvm / 16 + 255) / 256 + 1), 256, 0,
                                   b->stream>>>(b->d_defect, b->d_border, b->d_lb, q.d_pack + q.scal, cvm,
-                                               reinterpret_cast<const uint32_t *>(b->d_sc), scw,
-                                               reinterpret_cast<const uint32_t *>(b->d_st), stw,
-                                               reinterpret_cast<uint32_t *>(q.d_pack));
+                                               reinterpret_cast<const uint32_t *>(b->d_sc.get()), scw,
+                                               reinterpret_cast<const uint32_t *>(b->d_st.get()), stw,
+                                               reinterpret_cast<uint32_t *>(q.d_pack.get()));
                     HIP_TRY(hipGetLastError());
                 }
                 HIP_TRY(hipEventRecord(q.packed, b->stream));
@@ -1719,7 +1674,7 @@ int vh_pipe_run(vh_pipe *p, const float *hp, const uint8_t *mask, int64_t n, con
             };
             auto back = [&](Chunk &c) {
                 const float *dn4 = opts->do_n4 ? b->d_n4 : b->d_hp;
-                c.sp[2].d2h((const char *)dn4, (char *)q.n4, b->stream);
+                c.sp[2].d2h((const char *)dn4, (char *)q.n4.get(), b->stream);
                 if (maps || res)   // one D2H: the scalars / states block, then the packed maps
                     HIP_TRY(hipMemcpyAsync(q.u8 + sub * V, q.d_pack, q.scal + (maps ? c.CV : 0),
                                            hipMemcpyDeviceToHost, b->stream));
@@ -1731,7 +1686,7 @@ int vh_pipe_run(vh_pipe *p, const float *hp, const uint8_t *mask, int64_t n, con
                     fill_results_from(b, q.sc, q.st, q.res.data());
                     memcpy(res + c.v0, q.res.data(), sizeof(vh_vdp_result) * c.cnt);
                 }
-                c.sp[2].d2h_finish((const char *)q.n4);
+                c.sp[2].d2h_finish((const char *)q.n4.get());
                 if (maps)
                     par_unpack_maps(qd, defect ? defect + c.v0 * V : nullptr,
                                     defect_border ? defect_border + c.v0 * V : nullptr,
@@ -1816,22 +1771,19 @@ int vh_link_probe(vh_ctx *ctx, int64_t bytes, double out_gbps[3]) {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!out_gbps || bytes <= 0) throw VhError{VH_ERR_ARG, "link probe: bad arguments"};
         HIP_TRY(hipSetDevice(ctx->device));
-        void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+        Buf<char, 1> h_in, h_out;   // (freed after release(), as the scope ends)
+        Buf<char> d_in, d_out;
         hipStream_t s[2] = {nullptr, nullptr};
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         auto release = [&]() {
             for (auto e : ev) if (e) (void)hipEventDestroy(e);
             for (auto x : s) if (x) (void)hipStreamDestroy(x);
-            if (h_in) (void)hipHostFree(h_in);
-            if (h_out) (void)hipHostFree(h_out);
-            if (d_in) (void)hipFree(d_in);
-            if (d_out) (void)hipFree(d_out);
         };
         try {
-            HIP_TRY(hipHostMalloc(&h_in, (size_t)bytes, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(&h_out, (size_t)bytes, hipHostMallocDefault));
-            HIP_TRY(hipMalloc(&d_in, (size_t)bytes));
-            HIP_TRY(hipMalloc(&d_out, (size_t)bytes));
+            h_in.reserve((size_t)bytes);
+            h_out.reserve((size_t)bytes);
+            d_in.reserve((size_t)bytes);
+            d_out.reserve((size_t)bytes);
             std::memset(h_in, 1, (size_t)bytes);
             std::memset(h_out, 2, (size_t)bytes);
             for (auto &x : s) HIP_TRY(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));

@@ -413,9 +413,9 @@ vh_ci_table *vh_ci_table_build(vh_ctx *ctx, int64_t R, int64_t C, const int16_t 
     t->rows = rows;
     t->nbs = nbs;
     try {
-        HIP_TRY(hipMalloc(&t->d_offL, sizeof(int32_t) * rows));
-        HIP_TRY(hipMalloc(&t->d_bounds, sizeof(int32_t) * nbs));
-        HIP_TRY(hipMalloc(&t->d_radii, sizeof(double) * nbs));
+        t->d_offL.reserve((size_t)rows);
+        t->d_bounds.reserve((size_t)nbs);
+        t->d_radii.reserve((size_t)nbs);
         HIP_TRY(hipMemcpy(t->d_offL, offL.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(t->d_bounds, bounds, sizeof(int32_t) * nbs, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(t->d_radii, radii, sizeof(double) * nbs, hipMemcpyHostToDevice));
@@ -429,9 +429,6 @@ vh_ci_table *vh_ci_table_build(vh_ctx *ctx, int64_t R, int64_t C, const int16_t 
 void vh_ci_table_free(vh_ci_table *t) {
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
-    if (t->d_offL) (void)hipFree(t->d_offL);
-    if (t->d_bounds) (void)hipFree(t->d_bounds);
-    if (t->d_radii) (void)hipFree(t->d_radii);
     delete t;
 }
 
@@ -448,29 +445,20 @@ void vh_ci_run(vh_batch *b, const vh_ci_table *t, double minvox, double *d_ci, V
     hipStream_t st = b->stream;
     const int64_t words = (b->V + 31) / 32, rows = t->rows, nbs = t->nbs;
     // workspace owned by the batch (freed with it): no allocation, and nothing to leak, per call
-    if (!b->d_ci_status) {
-        HIP_TRY(hipMalloc(&b->d_ci_status, sizeof(int32_t) * b->nb));
-        HIP_TRY(hipMalloc(&b->d_ci_count, sizeof(unsigned long long) * b->nb));
-    }
+    const size_t nb = (size_t)b->nb;
+    b->d_ci_status.reserve(nb);
+    b->d_ci_count.reserve(nb);
     int32_t *d_status = b->d_ci_status;
     unsigned long long *d_count = b->d_ci_count;
-    if (!b->d_bitmap) {
-        HIP_TRY(hipMalloc(&b->d_bitmap, sizeof(uint32_t) * b->nb * words));
-        HIP_TRY(hipMalloc(&b->d_ci_list, sizeof(int32_t) * b->nb * b->V));
-    }
-    if (!form && !b->d_ci_shell) HIP_TRY(hipMalloc(&b->d_ci_shell, sizeof(int32_t) * b->nb * b->V));
-    if (form && !b->d_ci_shell16) {
-        HIP_TRY(hipMalloc(&b->d_ci_shell16, sizeof(int16_t) * b->nb * b->V));
-        HIP_TRY(hipMalloc(&b->d_ci_next, sizeof(uint32_t) * CIB_NEXT_STRIDE * b->nb));
+    b->d_bitmap.reserve(nb * words);
+    b->d_ci_list.reserve(nb * b->V);
+    if (!form) b->d_ci_shell.reserve(nb * b->V);
+    if (form) {
+        b->d_ci_shell16.reserve(nb * b->V);
+        b->d_ci_next.reserve(CIB_NEXT_STRIDE * nb);
     }
     int16_t *d_s16 = form ? b->d_ci_shell16 : nullptr;
-    if (nbs > b->ci_nb_cap) {
-        if (b->d_ci_hist) HIP_TRY(hipFree(b->d_ci_hist));
-        b->d_ci_hist = nullptr;
-        b->ci_nb_cap = 0;
-        HIP_TRY(hipMalloc(&b->d_ci_hist, sizeof(uint32_t) * b->nb * nbs));
-        b->ci_nb_cap = nbs;
-    }
+    b->d_ci_hist.reserve(nb * nbs);
     {
         const int64_t big = std::max<int64_t>(b->nb * words, b->nb * nbs);
         k_ci_clear<<<(unsigned)std::min<int64_t>((big + VH_TPB - 1) / VH_TPB, 1024), VH_TPB, 0, st>>>(

@@ -266,13 +266,6 @@ __global__ __launch_bounds__(VH_TPB) void k_montage(MontageArgs a, const uint64_
     o[2] = np_u8(bv * 255.0);
 }
 
-static void *dcopy(const void *h, size_t bytes, hipStream_t s) {
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes ? bytes : 1));
-    if (h && bytes) HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    return d;
-}
-
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
                     const void *hp, int h64, const float *n4, const uint8_t *mborder,
                     const uint8_t *def, const double *ci, const double *parula, int64_t prow,
@@ -286,10 +279,12 @@ void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *
     if (prow <= 0) throw VhError{VH_ERR_ARG, "montage: empty colour table"};
     a.p64 = p64; a.h64 = h64; a.prow = prow;
     const size_t V = (size_t)(R * C * Z);
-    std::vector<void *> owned;
-    auto up = [&](const void *h, size_t bytes) {
-        void *d = dcopy(h, bytes, s);
-        owned.push_back(d);
+    std::vector<Buf<char>> owned;   // freed as the call ends, the stream drained on every path
+    auto up = [&](const void *h, size_t bytes) -> void * {
+        owned.emplace_back();
+        owned.back().reserve(bytes);
+        char *d = owned.back();
+        if (h && bytes) HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
         return d;
     };
     int32_t herr = 0;
@@ -317,10 +312,8 @@ void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *
         HIP_TRY(hipStreamSynchronize(s));
     } catch (...) {
         (void)hipStreamSynchronize(s);
-        for (void *p : owned) (void)hipFree(p);
         throw;
     }
-    for (void *p : owned) (void)hipFree(p);
     if (herr & 2) throw VhError{VH_ERR_ARG, "cannot convert float NaN to integer (CI colour index)"};
     if (herr & 1) throw VhError{VH_ERR_INDEX, "CI colour index out of range of the colour table "
                                               "(int(CI*64/40), Vent_Analysis.py:482-484)"};

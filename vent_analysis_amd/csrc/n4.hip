@@ -92,6 +92,7 @@ int vh_level_ncp(const vh_n4_params &p, int level, int axis) {
 
 void vh_n4_prepare_tables(vh_batch *b, const vh_n4_params &prm) {
     if (b->tabs_valid && same_params(b->tab_prm, prm)) return;
+    b->tabs_valid = false;   // until the new tables are resident (a failed allocation leaves none)
     const int64_t dims[3] = {b->R, b->C, b->Z};
     std::vector<uint8_t> blob;
     b->tab_off.assign((size_t)prm.n_levels * 3 * 8, 0);
@@ -166,18 +167,17 @@ void vh_n4_prepare_tables(vh_batch *b, const vh_n4_params &prm) {
         b->lvx_off[L * 3 + 1] = push(wk3.data(), wk3.size() * 8);
         b->lvx_off[L * 3 + 2] = push(wk2.data(), wk2.size() * 8);
     }
-    if (b->d_tabs) HIP_TRY(hipFree(b->d_tabs));
-    b->d_tabs = nullptr;
-    HIP_TRY(hipMalloc(&b->d_tabs, blob.size()));
+    // always a new block: the free waits for the device, so no earlier launch still reads the old tables
+    b->d_tabs.reset();
+    b->d_tabs.reserve(blob.size());
     HIP_TRY(hipMemcpy(b->d_tabs, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    if (!b->d_twiddle) {
+    if (b->d_twiddle.reserve(VH_FFT_P / 2)) {
         std::vector<double2> tw(VH_FFT_P / 2);
         for (int k = 0; k < VH_FFT_P / 2; ++k) {
             const double a = 2.0 * M_PI * (double)k / (double)VH_FFT_P;
             tw[k].x = cos(a);
             tw[k].y = -sin(a);
         }
-        HIP_TRY(hipMalloc(&b->d_twiddle, sizeof(double2) * tw.size()));
         HIP_TRY(hipMemcpy(b->d_twiddle, tw.data(), sizeof(double2) * tw.size(),
                           hipMemcpyHostToDevice));
     }
@@ -188,7 +188,7 @@ void vh_n4_prepare_tables(vh_batch *b, const vh_n4_params &prm) {
 DevLevel vh_dev_level(const vh_batch *b, const vh_n4_params &prm, int L) {
     DevLevel lv;
     const int64_t dims[3] = {b->R, b->C, b->Z};
-    const uint8_t *base = (const uint8_t *)b->d_tabs;
+    const uint8_t *base = (const uint8_t *)b->d_tabs.get();
     for (int a = 0; a < 3; ++a) {
         lv.ax[a].base = (const int32_t *)(base + b->tab_off[(L * 3 + a) * 8 + 0]);
         lv.ax[a].w = (const float *)(base + b->tab_off[(L * 3 + a) * 8 + 1]);
@@ -216,52 +216,49 @@ void vh_ensure_n4_workspace(vh_batch *b, const vh_n4_params &prm) {
     b->rsh = 1;   // compact voxel index = (row << rsh) | column
     while (((int64_t)1 << b->rsh) < b->CZ) ++b->rsh;
     if (b->R >= ((int64_t)1 << (31 - b->rsh))) throw VhError{VH_ERR_ARG, "N4: rows x columns too large for the packed voxel index"};
-    if (b->d_L0 == nullptr) {
-        b->VS = (b->V + 63) & ~(int64_t)63;   // compact-array stride: 256-byte aligned volumes
-        const int64_t nch = b->nb * ((b->VS + N4_CH - 1) / N4_CH);
-        HIP_TRY(hipMalloc(&b->d_L0, sizeof(float) * b->nb * b->VS));
-        // U and D three times: the study driver speculates up to two iterations past the last
-        // decided one (rings of 3); the sweep driver keeps PC's p values in D's second third
-        HIP_TRY(hipMalloc(&b->d_U, sizeof(float) * 3 * b->nb * b->VS));
-        HIP_TRY(hipMalloc(&b->d_D, sizeof(float) * 3 * b->nb * b->VS));
-        HIP_TRY(hipMalloc(&b->d_perm, sizeof(int32_t) * b->nb * b->VS));
-        HIP_TRY(hipMalloc(&b->d_ridx, sizeof(int32_t) * b->nb * b->VS));
-        HIP_TRY(hipMalloc(&b->d_cp, sizeof(int32_t) * (b->nb + 1)));
-        HIP_TRY(hipMalloc(&b->d_cvol, sizeof(int32_t) * nch));
-        HIP_TRY(hipMalloc(&b->d_hpart, sizeof(uint64_t) * nch * VH_MAX_BINS));
-        HIP_TRY(hipMalloc(&b->d_cpart, sizeof(double) * 2 * nch));
-        HIP_TRY(hipMalloc(&b->d_E, sizeof(float) * b->nb * VH_MAX_BINS));
-        HIP_TRY(hipMalloc(&b->d_st, sizeof(N4State) * b->nb));
-        HIP_TRY(hipMalloc(&b->d_nactive, sizeof(int32_t) * 8 * 1024));
-    }
+    b->VS = (b->V + 63) & ~(int64_t)63;   // compact-array stride: 256-byte aligned volumes
+    const size_t nb = (size_t)b->nb, nch = nb * ((b->VS + N4_CH - 1) / N4_CH);
+    // fixed by the batch's shape: each allocates on the first call (or the first after its own
+    // allocation failed) and holds ever after
+    b->d_L0.reserve(nb * b->VS);
+    // U and D three times: the study driver speculates up to two iterations past the last
+    // decided one (rings of 3); the sweep driver keeps PC's p values in D's second third
+    b->d_U.reserve(3 * nb * b->VS);
+    b->d_D.reserve(3 * nb * b->VS);
+    b->d_perm.reserve(nb * b->VS);
+    b->d_ridx.reserve(nb * b->VS);
+    b->d_cp.reserve(nb + 1);
+    b->d_cvol.reserve(nch);
+    b->d_hpart.reserve(nch * VH_MAX_BINS);
+    b->d_cpart.reserve(2 * nch);
+    b->d_E.reserve(nb * VH_MAX_BINS);
+    b->d_st.reserve(nb);
+    b->d_nactive.reserve(8 * 1024);
+    // by the lattice: a stride is the largest request so far, named once every buffer it indexes
+    // holds that much and 0 in between, so a failed allocation makes the next call redo the group
     if (lat > b->lat_cap) {
-        if (b->d_lat) HIP_TRY(hipFree(b->d_lat));
-        if (b->d_numfix) HIP_TRY(hipFree(b->d_numfix));
-        if (b->d_den) HIP_TRY(hipFree(b->d_den));
-        HIP_TRY(hipMalloc(&b->d_lat, sizeof(float) * 3 * b->nb * lat));   // lattice + 2 scratch
-        HIP_TRY(hipMalloc(&b->d_numfix, sizeof(uint64_t) * 2 * b->nb * lat));
-        HIP_TRY(hipMalloc(&b->d_den, sizeof(double) * b->nb * lat));
+        b->lat_cap = 0;
+        b->d_lat.reset();
+        b->d_numfix.reset();
+        b->d_den.reset();
+        b->d_lat.reserve(3 * nb * lat);   // lattice + 2 scratch
+        b->d_numfix.reserve(2 * nb * lat);
+        b->d_den.reserve(nb * lat);
         b->lat_cap = lat;
     }
     if (cx > 64) throw VhError{VH_ERR_ARG, "N4 lattice too fine: > 64 control points along rows"};
-    const int64_t ntiles = (b->CZ + TILE_W - 1) / TILE_W;
-    if (b->d_rowstart == nullptr || b->n4_tiles != ntiles) {
-        if (b->d_rowstart) HIP_TRY(hipFree(b->d_rowstart));
-        if (b->d_rowmask) HIP_TRY(hipFree(b->d_rowmask));
-        if (b->d_rrank) HIP_TRY(hipFree(b->d_rrank));
-        HIP_TRY(hipMalloc(&b->d_rowstart, sizeof(int32_t) * b->nb * ntiles * b->R));
-        HIP_TRY(hipMalloc(&b->d_rowmask, sizeof(uint64_t) * b->nb * ntiles * b->R));
-        HIP_TRY(hipMalloc(&b->d_rrank, sizeof(int32_t) * b->nb * ntiles * b->R));
-        b->n4_tiles = ntiles;
-    }
+    b->n4_tiles = (b->CZ + TILE_W - 1) / TILE_W;
+    b->d_rowstart.reserve(nb * b->n4_tiles * b->R);
+    b->d_rowmask.reserve(nb * b->n4_tiles * b->R);
+    b->d_rrank.reserve(nb * b->n4_tiles * b->R);
     if (cx * b->CZ > b->t_cap) {
-        if (b->d_T) HIP_TRY(hipFree(b->d_T));
-        HIP_TRY(hipMalloc(&b->d_T, sizeof(float) * 2 * b->nb * cx * b->CZ));
+        b->t_cap = 0;
+        b->d_T.reserve(2 * nb * cx * b->CZ);
         b->t_cap = cx * b->CZ;
     }
     if (q2 > b->q2_cap) {
-        if (b->d_P1) HIP_TRY(hipFree(b->d_P1));
-        HIP_TRY(hipMalloc(&b->d_P1, sizeof(double) * b->nb * q2));
+        b->q2_cap = 0;
+        b->d_P1.reserve(nb * q2);
         b->q2_cap = q2;
     }
     vh_n4_prepare_tables(b, prm);
@@ -1981,7 +1978,7 @@ static void n4_subbatch(vh_batch *b, const vh_n4_params &prm, int64_t vol0, int6
     float *U = b->d_U;
     std::vector<hipEvent_t> evs;
     std::vector<int> ev_slot;   // iteration slot (d_nactive / h_flags index) behind each event
-    if (!b->h_flags) HIP_TRY(hipHostMalloc((void **)&b->h_flags, sizeof(int32_t) * 1024));
+    b->h_flags.reserve(1024);
     volatile int32_t *hflag = b->h_flags;   // written by k_n4_emap through its device mapping
     int32_t *dflag = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void **)&dflag, b->h_flags, 0));
@@ -1990,14 +1987,7 @@ static void n4_subbatch(vh_batch *b, const vh_n4_params &prm, int64_t vol0, int6
     for (int64_t v = vol0; v < vol0 + ns; ++v) max_ch = std::max(max_ch, hcp[v + 1] - hcp[v]);
     uint64_t *hred = nullptr;
     if (max_ch >= 4 * N4_HSL) {
-        const size_t need = sizeof(uint64_t) * (size_t)ns * N4_HSL * 2 * VH_MAX_BINS;
-        if (need > b->hred_cap) {
-            if (b->d_hred) HIP_TRY(hipFree(b->d_hred));
-            b->d_hred = nullptr;
-            b->hred_cap = 0;
-            HIP_TRY(hipMalloc(&b->d_hred, need));
-            b->hred_cap = need;
-        }
+        b->d_hred.reserve((size_t)ns * N4_HSL * 2 * VH_MAX_BINS);
         hred = b->d_hred;
     }
     int total_iters = 0;
@@ -2063,14 +2053,8 @@ static void n4_subbatch(vh_batch *b, const vh_n4_params &prm, int64_t vol0, int6
                 const size_t need = NB * (6 * sizeof(float) + 2 * sizeof(double)) +
                                     (size_t)pcg_grid * (3 * sizeof(double) + sizeof(int)) + 256 +
                                     2 * (size_t)pcg_grid * sizeof(PcgWg) + 2 * (size_t)NB * sizeof(float) + 256;
-                if ((int64_t)need > b->pcg_cap) {
-                    if (b->d_pcg) HIP_TRY(hipFree(b->d_pcg));
-                    b->d_pcg = nullptr;
-                    b->pcg_cap = 0;
-                    HIP_TRY(hipMalloc(&b->d_pcg, need));
-                    b->pcg_cap = (int64_t)need;
-                }
-                char *w = (char *)b->d_pcg;
+                b->d_pcg.reserve(need);
+                char *w = b->d_pcg;
                 pcg_args.s1 = (double *)w; w += NB * sizeof(double);
                 pcg_args.s2 = (double *)w; w += NB * sizeof(double);
                 pcg_args.agA = (double *)w; w += pcg_grid * sizeof(double);
@@ -2256,13 +2240,7 @@ void vh_launch_n4(vh_batch *b, const vh_n4_params &prm) {
         } else {   // large volumes: chunked scans over the GPU
             const int64_t ncs = (nrs + RS_CH - 1) / RS_CH, nrc = (ntiles + RR_CH - 1) / RR_CH;
             const int64_t need = b->nb * std::max(ncs, (nrc + 1) * b->R);
-            if (need > b->iscan_cap) {
-                if (b->d_iscan) HIP_TRY(hipFree(b->d_iscan));
-                b->d_iscan = nullptr;
-                b->iscan_cap = 0;
-                HIP_TRY(hipMalloc(&b->d_iscan, sizeof(int32_t) * need));
-                b->iscan_cap = need;
-            }
+            b->d_iscan.reserve((size_t)need);
             const dim3 gs((unsigned)ncs, (unsigned)b->nb), gr((unsigned)nrc, (unsigned)b->nb);
             k_n4_rowscan_parts<<<gs, VH_TPB, 0, st>>>(b->d_rowstart, nrs, b->d_iscan, ncs);
             VH_CHECK_LAUNCH();

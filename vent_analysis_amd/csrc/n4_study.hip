@@ -1559,10 +1559,10 @@ static StudyArgs study_args(vh_batch *b, const vh_n4_params &prm, const StudyLay
         h.max_iters[L] = prm.max_iters[L];
         h.lv[L] = vh_dev_level(b, prm, L);
     }
-    if (!b->d_study_lv) HIP_TRY(hipMalloc(&b->d_study_lv, sizeof(StudyLevels)));
+    b->d_study_lv.reserve(sizeof(StudyLevels));
     HIP_TRY(hipMemcpyAsync(b->d_study_lv, &h, sizeof(StudyLevels), hipMemcpyHostToDevice,
                            b->stream));
-    a.lvs = (const StudyLevels *)b->d_study_lv;
+    a.lvs = (const StudyLevels *)b->d_study_lv.get();
     // global state of the study: the fit denominators and the two T-window buffers (the sweep
     // driver's d_den / d_T, vh_ensure_n4_workspace)
     const int Lf = prm.n_levels - 1;
@@ -1586,16 +1586,14 @@ void vh_launch_n4_study(vh_batch *b, const vh_n4_params &prm) {
     if (!study_layout(b, prm, Ly)) throw VhError{VH_ERR_ARG, "N4 study kernel: LDS budget exceeded"};
     StudyArgs a = study_args(b, prm, Ly);
     if (b->nb > 1 && b->nb <= 4096) {
-        if (!b->d_study_order) HIP_TRY(hipMalloc(&b->d_study_order, sizeof(int32_t) * b->nb));
+        b->d_study_order.reserve((size_t)b->nb);
         k_study_order<<<1, 1024, 0, b->stream>>>(b->d_sc, b->nb, b->d_study_order);
         VH_CHECK_LAUNCH();
         a.order = b->d_study_order;
     }
     if (PC_DRIFT) {
-        if (!b->d_pcdrift) {
-            HIP_TRY(hipMalloc(&b->d_pcdrift, sizeof(float) * ST_TPB * b->nb));
+        if (b->d_pcdrift.reserve((size_t)ST_TPB * b->nb))
             HIP_TRY(hipMemsetAsync(b->d_pcdrift, 0, sizeof(float) * ST_TPB * b->nb, b->stream));
-        }
         a.pcdrift = b->d_pcdrift;
     }
     vh_set_max_lds((const void *)k_n4_study, ST_MAX_LDS);
@@ -1661,17 +1659,11 @@ void vh_launch_n4_studyg(vh_batch *b, const vh_n4_params &prm) {
     const size_t b_e = A256(sizeof(float) * 2 * (size_t)NB);
     const size_t b_p = A256(sizeof(float) * ((size_t)b->VS + (size_t)NB));   // (L + 1) NB <= n + NB
     const size_t need = b_h + b_n + b_g + b_r + b_i + b_w + b_e + b_p;
-    if ((int64_t)need > b->stg_cap) {
-        if (b->d_stg) HIP_TRY(hipFree(b->d_stg));
-        b->d_stg = nullptr;
-        b->stg_cap = 0;
-        HIP_TRY(hipMalloc(&b->d_stg, need));
-        b->stg_cap = (int64_t)need;
-    }
+    b->d_stg.reserve(need);
     vh_set_max_lds((const void *)k_n4_studyg, (int)(ST_MAX_LDS - sizeof(Pcg2Lds)));
     for (int64_t v = 0; v < b->nb; ++v) {   // one study per launch (the class and configs 2 / 5: one)
         ScopedKTimer tm(b, "n4_study", 0.0, true);   // stamped: a cooperative launch
-        char *w = (char *)b->d_stg;
+        char *w = b->d_stg;
         StudyGrid gd{};
         gd.hsum = (unsigned long long *)w; w += b_h;
         gd.nsum = (unsigned long long *)w; w += b_n;

@@ -1539,7 +1539,7 @@ bool vh_launch_defect_select(vh_batch *b, const float *d_n4, float thresh, int s
     PsGeom g; dim3 grid; size_t lds;
     if (!plane_geometry(b, PS_SEL, g, grid, lds)) return false;
     hipStream_t st = b->stream;
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(b->d_tilecnt);   // free after the sort
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(b->d_tilecnt.get());   // free after the sort
     HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 2 * b->nb, st));
     {
         ScopedKTimer tm(b, "defect_sel", (km ? 8.0 : 7.0) * (double)b->V);
@@ -2424,7 +2424,7 @@ static void vh_launch_kmeans(vh_batch *b, hipStream_t st) {
     ScopedKTimer tm(b, "kmeans", 0.0, false, st);
     const int64_t max_ktiles = (b->V + KM_TILE - 1) / KM_TILE;
     // free after the sort: 4V bytes per volume >= 8 (V / 1024 + 1)
-    double *scratch = reinterpret_cast<double *>(b->d_keys1);
+    double *scratch = reinterpret_cast<double *>(b->d_keys1.get());
     if (max_ktiles > KM_LDS_TILES) {
         k_km_tiles<<<dim3((unsigned)((max_ktiles + KM_TPB / 64 - 1) / (KM_TPB / 64)), (unsigned)b->nb),
                      KM_TPB, 0, st>>>(b->d_keys0, b->V, scratch, max_ktiles, b->d_sc);
@@ -2453,14 +2453,8 @@ void vh_launch_vdp_chain(vh_batch *b, const float *d_n4, const vh_run_opts &o) {
         ScopedKTimer tm(b, "sort", 0.0);
         if (b->nb == 1 && b->V >= ((int64_t)1 << 20)) {   // one large volume: the grid sort
             const int64_t nchunk = (b->V + VSG_CHUNK - 1) / VSG_CHUNK;
-            if (b->sortg_cap < nchunk * 256) {
-                if (b->d_sortg) HIP_TRY(hipFree(b->d_sortg));
-                b->d_sortg = nullptr;
-                b->sortg_cap = 0;
-                HIP_TRY(hipMalloc(&b->d_sortg, sizeof(uint32_t) * nchunk * 256));
-                b->sortg_cap = nchunk * 256;
-            }
-            uint32_t *cnt = (uint32_t *)b->d_sortg;
+            b->d_sortg.reserve(sizeof(uint32_t) * nchunk * 256);
+            uint32_t *cnt = (uint32_t *)b->d_sortg.get();
             uint32_t *kin = b->d_keys0, *kout = b->d_keys1;
             for (int p = 0; p < 4; ++p) {
                 k_sortg_count<<<(unsigned)nchunk, VS_TPB, 0, st>>>(kin, b->d_sc, 0, 8 * p, cnt);
@@ -2479,7 +2473,7 @@ void vh_launch_vdp_chain(vh_batch *b, const float *d_n4, const vh_run_opts &o) {
     {
         ScopedKTimer tm(b, "mean", 0.0);
         const int64_t max_chunks = (b->V + 8191) / 8192;
-        float *chunk = reinterpret_cast<float *>(b->d_part);   // part holds >= nb*max_chunks floats
+        float *chunk = reinterpret_cast<float *>(b->d_part.get());   // part holds >= nb*max_chunks floats
         k_chunk_sums<<<dim3((unsigned)((max_chunks + VH_TPB / 64 - 1) / (VH_TPB / 64)), (unsigned)b->nb),
                        VH_TPB, 0, st>>>(b->d_keys0, b->d_sc, b->V, max_chunks, chunk);
         VH_CHECK_LAUNCH();
@@ -2500,7 +2494,7 @@ void vh_launch_vdp_chain(vh_batch *b, const float *d_n4, const vh_run_opts &o) {
     // the sweep for the same reason, 35 -> 24 us)
     if (o.do_kmeans) vh_launch_kmeans(b, st);
     {
-        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(b->d_tilecnt);
+        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(b->d_tilecnt.get());
         HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 2 * b->nb, st));
         int tz; dim3 grid; size_t lds;
         tile_geometry(b, o.morph3d != 0, tz, grid, lds);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/vent_hip.h"
+#include "devbuf.h"
 
 #define VH_TPB 256          // threads per block for streaming kernels (4 waves of 64)
 #define VH_WAVE 64
@@ -143,8 +144,7 @@ struct vh_ctx {
     void *comm = nullptr;           // ncclComm_t
     int nranks = 1, rank = 0;
     // page-locked, device-mapped CI scalars (k_ci_finish stores them there: no readback copy)
-    VolScalars *h_ci_sc = nullptr;
-    int64_t h_ci_sc_cap = 0;
+    Buf<VolScalars, 1> h_ci_sc;
     // the host-buffer entry points (vh_n4, vh_vdp, ...) share one cached scratch batch per
     // context; mu serialises them, so a context may be used from several host threads
     vh_batch *scratch = nullptr;
@@ -160,21 +160,20 @@ struct vh_ctx {
     // flight would otherwise issue them on their own streams, which the GPU may run in a different
     // order than another rank does: a deadlock)
     hipStream_t comm_st = nullptr;
-    void *recon_buf = nullptr;
-    size_t recon_cap = 0;
+    Buf<char> recon_buf;
 };
 
 struct vh_pipe {
     struct Slot {
         vh_batch *b = nullptr;
-        float *hp = nullptr, *n4 = nullptr;   // pinned staging [sub][V]
-        uint8_t *u8 = nullptr;                // pinned: mask in [sub][V], then the D2H block (scal + [sub][V])
+        Buf<float, 1> hp, n4;                 // pinned staging [sub][V]
+        Buf<uint8_t, 1> u8;                   // pinned: mask in [sub][V], then the D2H block (scal + [sub][V])
         hipEvent_t done = nullptr;            // recorded after the slot's current chunk's pipeline
         hipEvent_t h2d = nullptr;             // recorded after the slot's current chunk's H2D
         hipEvent_t packed = nullptr;          // recorded after the chunk's output packing (its D2H may start)
-        uint8_t *d_pack = nullptr;            // device: the chunk's D2H block: scalars (scal bytes), packed maps
+        Buf<uint8_t> d_pack;                  // device: the chunk's D2H block: scalars (scal bytes), packed maps
         size_t scal = 0;                      // bytes of the per-study scalars + N4 states block (4 KiB multiple)
-        uint8_t *mb = nullptr;                // pinned: mask bits, two chunks' worth (double buffer)
+        Buf<uint8_t, 1> mb;                   // pinned: mask bits, two chunks' worth (double buffer)
         size_t mb_half = 0;
         VolScalars *sc = nullptr;             // the chunk's per-study scalars / N4 states: views into u8
         N4State *st = nullptr;
@@ -208,115 +207,109 @@ struct vh_batch {
     hipStream_t st_n4 = nullptr;     // VH_PRIO: the study kernel alone on a low-priority stream (the
     hipEvent_t ev_n4_pre = nullptr, ev_n4_post = nullptr;   // rest on a high-priority one), joined by events
     hipEvent_t ev_cpre = nullptr, ev_cpost = nullptr;      // the cohort all-reduce on vh_ctx::comm_st
-    int32_t *h_flags = nullptr;      // pinned: the sweep driver's per-iteration active counts
+    // Every d_* member (and the pinned h_flags) is a Buf: the batch owns it, it is allocated by
+    // reserve() where it is first needed and freed by ~vh_batch.  Adding one takes the member alone.
+    Buf<int32_t, 1> h_flags;         // pinned: the sweep driver's per-iteration active counts
     int64_t R = 0, C = 0, Z = 0, V = 0, nb = 0, CZ = 0;
     int64_t max_tiles = 0;
     // inputs / outputs
-    float *d_hp = nullptr;
-    uint8_t *d_mask = nullptr;
-    float *d_n4 = nullptr;
-    uint8_t *d_defect = nullptr, *d_border = nullptr, *d_lb = nullptr;
+    Buf<float> d_hp;
+    Buf<uint8_t> d_mask;
+    Buf<float> d_n4;
+    Buf<uint8_t> d_defect, d_border, d_lb;
     // vh_batch_select_defect
-    uint8_t *d_km = nullptr;         // [nb][V] k-means labels (0 off-mask, else 1 + cluster), on first demand
-    const float *d_n4_last = nullptr;   // the N4 volume the last run's chain read (d_hp or d_n4)
+    Buf<uint8_t> d_km;               // [nb][V] k-means labels (0 off-mask, else 1 + cluster), on first demand
+    const float *d_n4_last = nullptr;   // (a view) the N4 volume the last run's chain read (d_hp or d_n4)
     bool km_valid = false;           // d_km holds the last run's labels
     bool sel_valid = false;          // a selection replaced the last run's maps (VolScalars::n_sel counts it)
     // mask statistics
-    int32_t *d_colrange = nullptr;   // [nb][CZ][2]  first/last masked row of each (col, slice) column
-    int32_t *d_colcount = nullptr;   // [nb][CZ]
-    uint32_t *d_colbits = nullptr;   // [nb][ceil(R/32)][CZ]  row bitmap of mask == 1 per column
-    uint32_t *d_colbnz = nullptr;    // [nb][ceil(R/32)][CZ]  row bitmap of mask != 0 per column
-    int64_t *d_colstart = nullptr;   // [nb][CZ]     exclusive prefix of colcount
-    uint8_t *d_rowany = nullptr, *d_colany = nullptr, *d_sliceany = nullptr;
-    VolScalars *d_sc = nullptr;
-    double *d_part = nullptr;        // [nb][part_blocks][4] deterministic partial sums
+    Buf<int32_t> d_colrange;         // [nb][CZ][2]  first/last masked row of each (col, slice) column
+    Buf<int32_t> d_colcount;         // [nb][CZ]
+    Buf<uint32_t> d_colbits;         // [nb][ceil(R/32)][CZ]  row bitmap of mask == 1 per column
+    Buf<uint32_t> d_colbnz;          // [nb][ceil(R/32)][CZ]  row bitmap of mask != 0 per column
+    Buf<int64_t> d_colstart;         // [nb][CZ]     exclusive prefix of colcount
+    Buf<uint8_t> d_rowany, d_colany, d_sliceany;
+    Buf<VolScalars> d_sc;
+    Buf<double> d_part;              // [nb][part_blocks][4] deterministic partial sums
     int64_t part_blocks = 0;
-    double *d_snrpart = nullptr;     // [nb][slab_blocks][4] SNR partial sums (k_snr / k_n4_final)
+    Buf<double> d_snrpart;           // [nb][slab_blocks][4] SNR partial sums (k_snr / k_n4_final)
     int64_t slab_blocks = 0;         // column blocks x 32-row slabs per volume
     bool snr_fused = false;          // k_n4_final computed the SNR partials of this run
     // sort
-    uint32_t *d_keys0 = nullptr, *d_keys1 = nullptr;
-    uint32_t *d_tilecnt = nullptr;   // [nb][256][max_tiles]
+    Buf<uint32_t> d_keys0, d_keys1;
+    Buf<uint32_t> d_tilecnt;         // [nb][256][max_tiles]
     // cohort
-    uint64_t *d_cohort = nullptr;
+    Buf<uint64_t> d_cohort;
     // N4 workspace
-    float *d_L0 = nullptr, *d_lat = nullptr, *d_E = nullptr;
-    unsigned long long *d_numfix = nullptr;   // [nb][lattice][2] 128-bit fixed-point fit sums (S5)
-    int32_t *d_rowstart = nullptr;   // [nb][tiles][R] compact offset of each (64-column tile, row)
-    uint64_t *d_rowmask = nullptr;   // [nb][tiles][R] mask == 1 lanes of each (tile, row)
-    int32_t *d_rrank = nullptr;      // [nb][tiles][R] raster rank of the first masked voxel of (tile, row)
-    int32_t *d_iscan = nullptr;      // large volumes: chunk sums of the row-start / raster-rank scans
-    int64_t iscan_cap = 0;
-    float *d_D = nullptr;            // [nb][VS] B_old - B_new (S7 input): compact order (n4), raster order (n4_study)
-    int32_t *d_perm = nullptr;       // [nb][VS] raster rank -> compact index of the mask == 1 voxels (n4)
+    Buf<float> d_L0, d_lat, d_E;
+    Buf<unsigned long long> d_numfix;   // [nb][lattice][2] 128-bit fixed-point fit sums (S5)
+    Buf<int32_t> d_rowstart;         // [nb][tiles][R] compact offset of each (64-column tile, row)
+    Buf<uint64_t> d_rowmask;         // [nb][tiles][R] mask == 1 lanes of each (tile, row)
+    Buf<int32_t> d_rrank;            // [nb][tiles][R] raster rank of the first masked voxel of (tile, row)
+    Buf<int32_t> d_iscan;            // large volumes: chunk sums of the row-start / raster-rank scans
+    Buf<float> d_D;                  // [nb][VS] B_old - B_new (S7 input): compact order (n4), raster order (n4_study)
+    Buf<int32_t> d_perm;             // [nb][VS] raster rank -> compact index of the mask == 1 voxels (n4)
     // compact N4 state: mask==1 voxels in tile-row order, volume stride VS
     int64_t VS = 0;
     int rsh = 1;                     // compact voxel index = (row << rsh) | column
     bool keys_fused = false;         // k_n4_final wrote the sort keys of binary-mask volumes
-    float *d_U = nullptr;            // [nb][VS] U = L0 - B
-    int32_t *d_ridx = nullptr;       // [nb][VS] raster index of each compact voxel
-    int32_t *d_cp = nullptr;         // [nb + 1] chunk prefix (N4_CH voxels per chunk)
-    int32_t *d_cvol = nullptr;       // [chunks] owning volume
-    uint64_t *d_hpart = nullptr;     // [chunks][VH_MAX_BINS] per-chunk histograms
-    uint64_t *d_hred = nullptr;      // [studies][N4_HSL][2][VH_MAX_BINS] slice sums (k_n4_hred)
-    size_t hred_cap = 0;
-    double *d_cpart = nullptr;       // [chunks][2] per-chunk convergence sums
-    int64_t n4_tiles = 0;
+    Buf<float> d_U;                  // [nb][VS] U = L0 - B
+    Buf<int32_t> d_ridx;             // [nb][VS] raster index of each compact voxel
+    Buf<int32_t> d_cp;               // [nb + 1] chunk prefix (N4_CH voxels per chunk)
+    Buf<int32_t> d_cvol;             // [chunks] owning volume
+    Buf<uint64_t> d_hpart;           // [chunks][VH_MAX_BINS] per-chunk histograms
+    Buf<uint64_t> d_hred;            // [studies][N4_HSL][2][VH_MAX_BINS] slice sums (k_n4_hred)
+    Buf<double> d_cpart;             // [chunks][2] per-chunk convergence sums
+    int64_t n4_tiles = 0;            // tiles the d_rowstart / d_rowmask / d_rrank rows were laid out for
     std::vector<size_t> lvx_off;     // per level: xst / wk3 / wk2 offsets in d_tabs
-    double *d_P1 = nullptr, *d_den = nullptr;
-    float *d_pcdrift = nullptr;      // [nb][1024] the study kernel's PC guess offsets (PC_DRIFT)
-    float *d_T = nullptr;            // [2][nb][CZ][ncx] per-column lattice contraction (new / previous field)
-    int64_t t_cap = 0;
-    N4State *d_st = nullptr;
-    int32_t *d_nactive = nullptr;
-    void *d_tabs = nullptr;          // device copy of all per-level axis tables
-    int64_t lat_cap = 0, q2_cap = 0;
+    Buf<double> d_P1, d_den;
+    Buf<float> d_pcdrift;            // [nb][1024] the study kernel's PC guess offsets (PC_DRIFT)
+    Buf<float> d_T;                  // [2][nb][CZ][ncx] per-column lattice contraction (new / previous field)
+    Buf<N4State> d_st;
+    Buf<int32_t> d_nactive;
+    Buf<char> d_tabs;                // device copy of all per-level axis tables
+    // per-study strides the kernels index with (the largest request so far), not capacities alone:
+    // lat_cap of d_lat / d_numfix / d_den, t_cap of d_T, q2_cap of d_P1.  0 while its group is empty.
+    int64_t lat_cap = 0, t_cap = 0, q2_cap = 0;
     std::vector<size_t> tab_off;     // offsets of each (level, axis) table in d_tabs
     vh_n4_params tab_prm{};          // parameters the tables were built for
     bool tabs_valid = false;
-    double2 *d_twiddle = nullptr;    // FFT twiddles (host-computed)
-    void *d_study_lv = nullptr;      // n4_study.hip: per-level table pointers + iteration caps
-    int32_t *d_study_order = nullptr;   // n4_study.hip: workgroup -> study, largest study first
-    void *d_pcg = nullptr;           // n4.hip k_n4_pcg: per-block guesses / ends / sums, aggregates
-    void *d_study_latg = nullptr;    // n4_study.hip depth 2: the lattice before the last two updates
-    size_t study_latg_cap = 0;
-    int64_t pcg_cap = 0;             // bytes of d_pcg
-    void *d_stg = nullptr;           // n4_study.hip grid form: global sums, records, grid-PC scratch
-    int64_t stg_cap = 0;             // bytes of d_stg
-    void *d_sortg = nullptr;         // vdp.hip grid sort: per-chunk digit counts / offsets
-    int64_t sortg_cap = 0;           // entries of d_sortg
+    Buf<double2> d_twiddle;          // FFT twiddles (host-computed)
+    Buf<char> d_study_lv;            // n4_study.hip: per-level table pointers + iteration caps
+    Buf<int32_t> d_study_order;      // n4_study.hip: workgroup -> study, largest study first
+    Buf<char> d_pcg;                 // n4.hip k_n4_pcg: per-block guesses / ends / sums, aggregates
+    Buf<char> d_study_latg;          // n4_study.hip depth 2: the lattice before the last two updates
+    Buf<char> d_stg;                 // n4_study.hip grid form: global sums, records, grid-PC scratch
+    Buf<char> d_sortg;               // vdp.hip grid sort: per-chunk digit counts / offsets
     // CI workspace
-    uint32_t *d_bitmap = nullptr;    // [nb][ceil(V/32)] Fortran-order defect bits
-    int32_t *d_ci_list = nullptr;    // [nb][V] defect voxel raster indices (compacted)
-    int32_t *d_ci_shell = nullptr;   // [nb][V]
-    uint32_t *d_ci_hist = nullptr;   // [nb][ci_nb]
-    int64_t ci_nb_cap = 0;
-    int32_t *d_ci_status = nullptr;  // [nb]
-    unsigned long long *d_ci_count = nullptr;   // [nb]
-    double *d_ci_map = nullptr;      // [nb][V] float64 CI map (vh_ci, vh_batch_download_ci)
+    Buf<uint32_t> d_bitmap;          // [nb][ceil(V/32)] Fortran-order defect bits
+    Buf<int32_t> d_ci_list;          // [nb][V] defect voxel raster indices (compacted)
+    Buf<int32_t> d_ci_shell;         // [nb][V]
+    Buf<uint32_t> d_ci_hist;         // [nb][ci_nb]
+    Buf<int32_t> d_ci_status;        // [nb]
+    Buf<unsigned long long> d_ci_count;   // [nb]
+    Buf<double> d_ci_map;            // [nb][V] float64 CI map (vh_ci, vh_batch_download_ci)
     // vh_batch_ci (the CI of the resident defect maps)
-    int16_t *d_ci_shell16 = nullptr; // [nb][V] shell of each defect voxel, -1 elsewhere
-    uint32_t *d_ci_next = nullptr;   // [nb][64] (one per 256 bytes) next unclaimed slot of the study's defect list (k_ci_walk_b)
-    double *d_ci_radii = nullptr;    // [ci_nbs] the last table's radii: the batch's own copy, so the
-    int64_t ci_radii_cap = 0;        //   float64 map can be expanded after the table is destroyed
+    Buf<int16_t> d_ci_shell16;       // [nb][V] shell of each defect voxel, -1 elsewhere
+    Buf<uint32_t> d_ci_next;         // [nb][64] (one per 256 bytes) next unclaimed slot of the study's defect list (k_ci_walk_b)
+    Buf<double> d_ci_radii;          // [ci_nbs] the last table's radii: the batch's own copy, so the
+                                     //   float64 map can be expanded after the table is destroyed
     int64_t ci_nbs = 0;
     double ci_minvox = 0.0;
     bool have_defect = false;        // vh_batch_set_defect uploaded the defect maps
     bool have_ci = false;            // vh_batch_ci has been enqueued
     // vh_batch_overlay / vh_batch_montage (export.hip): every buffer on first demand
     bool ci_fresh = false;           // vh_batch_ci was enqueued after the last change of the resident defect maps
-    uint8_t *d_ov_rgb = nullptr;     // [nb][Z][R][C][3] the overlay frames
-    uint32_t *d_ov_mm = nullptr;     // [nb][2] min / max of |N4| (float bits)
+    Buf<uint8_t> d_ov_rgb;           // [nb][Z][R][C][3] the overlay frames
+    Buf<uint32_t> d_ov_mm;           // [nb][2] min / max of |N4| (float bits)
     bool ov_valid = false;           // vh_batch_overlay has been enqueued since the last run
-    float *d_proton = nullptr;       // [nb][V] the montage's proton volumes
-    int32_t *d_mt_crop = nullptr;    // [nb][8] k_crop_layout: r0, nr, c0, nc, s0, ns, status, 0
-    MtStudy *d_mt_st = nullptr;      // [nb + 1]
-    uint32_t *d_mt_keys = nullptr;   // [nb][6] crop min / max keys of proton, HPvent, N4
-    int32_t *d_mt_flag = nullptr;    // [nb] 1: a CI colour index reached prow
-    double *d_mt_parula = nullptr;   // [mt_prow_cap][3]
-    int64_t mt_prow_cap = 0;
-    uint8_t *d_mt_img = nullptr;     // the compact image buffer, mt_img_cap bytes
-    int64_t mt_img_cap = 0;
+    Buf<float> d_proton;             // [nb][V] the montage's proton volumes
+    Buf<int32_t> d_mt_crop;          // [nb][8] k_crop_layout: r0, nr, c0, nc, s0, ns, status, 0
+    Buf<MtStudy> d_mt_st;            // [nb + 1]
+    Buf<uint32_t> d_mt_keys;         // [nb][6] crop min / max keys of proton, HPvent, N4
+    Buf<int32_t> d_mt_flag;          // [nb] 1: a CI colour index reached prow
+    Buf<double> d_mt_parula;         // [prow][3], the largest prow so far
+    Buf<uint8_t> d_mt_img;           // the compact image buffer
     std::vector<MtStudy> mt_st;      // host copy of d_mt_st (valid while mt_layout_valid)
     std::vector<int32_t> mt_status;  // [nb] VH_OK / VH_ERR_EMPTY of the layout
     bool mt_layout_valid = false;    // the layout is the last run's
@@ -329,7 +322,7 @@ struct vh_batch {
     std::map<std::string, KTimer> timers;
     // stamped timers (cooperative launches): [VH_KST_CAP] first-workgroup starts, then
     // [VH_KST_CAP] last-workgroup ends, device wall clock; kst_n slots handed out since the reset
-    unsigned long long *d_kst = nullptr;
+    Buf<unsigned long long> d_kst;
     int kst_n = 0;
     // last run options
     vh_run_opts opts{};
@@ -340,9 +333,9 @@ struct vh_batch {
 struct vh_ci_table {
     vh_ctx *ctx = nullptr;
     int64_t R = 0, C = 0, rows = 0, nbs = 0;
-    int32_t *d_offL = nullptr;       // [rows] px2vec offsets, CI_SENTINEL for duplicate rows
-    int32_t *d_bounds = nullptr;     // [nbs] shell prefix lengths
-    double *d_radii = nullptr;       // [nbs] r[b - 1]
+    Buf<int32_t> d_offL;             // [rows] px2vec offsets, CI_SENTINEL for duplicate rows
+    Buf<int32_t> d_bounds;           // [nbs] shell prefix lengths
+    Buf<double> d_radii;             // [nbs] r[b - 1]
     // vh_batch_ci: one event per batch that used the table, recorded on that batch's stream after
     // its CI launches (under ctx->mu); vh_ci_table_destroy waits on all of them before the frees
     mutable std::map<const vh_batch *, hipEvent_t> users;
