@@ -35,6 +35,11 @@
  *                from the resident buffers, with calculateBorder(mask) (:225-231) evaluated in place;
  *                only pixels come back.  Their kernel-timing classes are "overlay_b" and "montage_b"
  *                (vh_batch_kernel_time reads them; vh_batch_kernel_names does not list them)
+ *   vh_batch_distribution / vh_batch_download_distribution / vh_distribution  the histogram of the
+ *                normalised masked signal ("show histogram?", the open item of the reference's list,
+ *                Vent_Analysis.py:1019-1026), all six linear-binning class counts (:256; the reference
+ *                reports classes 1+2 only, :257) and the slice-wise mask / defect counts, per study from
+ *                the resident buffers (build-defined); kernel-timing class "dist_b", not listed either
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -298,6 +303,49 @@ int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int
  * index int(CI * 64 / 40) of the study's crop reached prow (the IndexError of Vent_Analysis.py:482-484):
  * that study's image bytes are unspecified, the other studies are unaffected. */
 int vh_batch_download_montage(vh_batch *b, uint8_t *image, int32_t *status);
+
+/* ---- the ventilation distribution of a device-resident batch -----------------------------------
+ * Per study the histogram of the normalised masked signal, and per slice the counts of mask, defect
+ * and linear-binning class voxels (slice-wise VDP): one read-only sweep over what the last vh_batch_run
+ * left resident; only counts come back, and every count is an exact integer.
+ *
+ * It reads N4, the volume the run's chain read (HPvent when do_n4 = 0); the resident mask (a voxel
+ * counts when mask != 0); the run's LB class volume; and the defect map as it stands (the run's,
+ * vh_batch_set_defect's or vh_batch_select_defect's).  The divisor d is the study's mean_anchor
+ * (VH_NORM_MEAN) or p99 (VH_NORM_P99) of that run.
+ *
+ * Histogram: for every voxel with mask != 0, nv = float32(x / d) (IEEE float32 division).  If
+ * nv >= 0 && nv < hi the voxel goes to bin min(n_bins - 1, (int)float32(nv * scale)), with
+ * scale = (float)n_bins / hi computed once in float32; nv < 0 goes to outside[i][0]; everything else
+ * to outside[i][1]: nv >= hi, NaN, and whatever a zero, infinite or NaN d gives under the same
+ * pointwise rule.  An empty-mask study gives zeros throughout.  With (VH_NORM_P99, VH_COHORT_BINS,
+ * 1.5f) a study's row is the row the cohort histogram (vh_run_opts.do_cohort) sums for it.
+ *
+ * Slice counts, over all voxels of slice z (mask or not): column 0 counts mask != 0, column 1
+ * defect != 0 (not ANDed with the mask: an uploaded map is counted as it is), columns 2..7 the LB
+ * classes 1..6 (a class byte outside 1..6 is counted nowhere).
+ *
+ * vh_batch_distribution enqueues only, and changes nothing the run, vh_batch_ci, the selection calls
+ * or the renderings wrote.  It may be called again with other parameters: the download returns the last
+ * call's result; a new run discards it.  VH_ERR_ARG, with nothing enqueued: a null batch, no
+ * vh_batch_run yet, norm not 0 or 1, n_bins outside 1..1024, hi not finite or <= 0, more than 1900
+ * slices.  vh_batch_download_distribution waits; VH_ERR_ARG when vh_batch_distribution has not been
+ * enqueued since the last run.  Its kernel-timing class is "dist_b" (vh_batch_kernel_time reads it;
+ * vh_batch_kernel_names does not list it).
+ *
+ * vh_distribution is the host-buffer form for one call, like vh_defect_map: the post-N4 chain (no N4,
+ * no SNR) on the scratch batch, then the above with that run's mean-anchored defect map; VH_ERR_EMPTY
+ * for an empty-mask study, like vh_vdp. */
+#define VH_NORM_MEAN 0   /* nv = float32(N4 / mean_anchor): the domain of calculate_VDP's thresh   */
+#define VH_NORM_P99  1   /* nv = float32(N4 / p99): the domain of the LB edges and of the cohort */
+#define VH_DIST_COLS 8   /* slice_counts columns: mask, defect, LB class 1..6 */
+int vh_batch_distribution(vh_batch *b, int norm, int32_t n_bins, float hi);
+int vh_batch_download_distribution(vh_batch *b, uint32_t *hist /* [nb][n_bins] */,
+                                   int64_t *outside /* [nb][2] */,
+                                   int64_t *slice_counts /* [nb][Z][VH_DIST_COLS] */);   /* all nullable */
+int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                    int64_t batch, float thresh, int norm, int32_t n_bins, float hi,
+                    uint32_t *hist, int64_t *outside, int64_t *slice_counts);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

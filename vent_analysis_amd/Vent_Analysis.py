@@ -250,6 +250,39 @@ class Vent_Analysis:
         self.defectArray = d[0].astype(np.float64) * v
         return 100 * np.sum(self.defectArray) / msum
 
+    def ventilation_distribution(self, norm='p99', bins=100, hi=1.5):
+        """The distribution behind the VDP numbers (build-defined; "show histogram?" is an open item
+        of the reference's list): the histogram of N4HPvent / d over the mask -- d the 99th percentile
+        (``norm`` 'p99', the domain of the linear-binning edges) or the mean anchor ('mean', the domain
+        of calculate_VDP's thresh) -- in ``bins`` bins of [0, hi), all six linear-binning class
+        fractions and the slice-wise VDP, counted on the GPU from N4HPvent, the mask and ``defectArray``
+        as it stands (select_defect's map included).  Needs calculate_VDP first.  Returns a dict and
+        sets nothing on the object: ``hist`` uint32 [bins]; ``edges`` float64 [bins + 1]; ``outside``
+        int64 [2] (masked voxels below 0; at or above hi, NaN included); ``slice_counts`` int64 [Z][8]
+        (mask, defect, LB class 1..6 per slice); ``lb_percent`` float64 [6], 100 * count / n_mask;
+        ``slice_vdp`` float64 [Z], 100 * defect_z / mask_z, NaN where the slice holds no mask;
+        ``vdp_from_slices``, 100 * sum(defect_z) / sum(mask_z)."""
+        if isinstance(self.N4HPvent, str) or isinstance(self.defectArray, str):
+            raise ValueError("ventilation_distribution: N4HPvent / defectArray are not set "
+                             "(run calculate_VDP first)")
+        norm = _lib.norm_source(norm)
+        mask_u8, _ = _mask_value(self.mask)
+        n4 = np.asarray(self.N4HPvent, dtype=np.float32)
+        with _lib.pooled_batch(*n4.shape, 1, device=self.device) as B:
+            B.upload(n4[None], mask_u8[None])
+            B.run(B.options(do_n4=False, do_snr=False, do_kmeans=False, vox=self.vox))
+            B.upload_defect((np.asarray(self.defectArray) != 0)[None])
+            B.distribution(norm, bins, hi)
+            out = B.download_distribution()
+        out = {k: (v if k == 'edges' else v[0]) for k, v in out.items()}
+        sl = out['slice_counts']
+        n_mask = np.float64(sl[:, 0].sum())
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out['lb_percent'] = 100 * sl[:, 2:].sum(axis=0).astype(np.float64) / n_mask
+            out['slice_vdp'] = np.where(sl[:, 0] > 0, 100 * sl[:, 1].astype(np.float64) / sl[:, 0], np.nan)
+            out['vdp_from_slices'] = 100 * np.float64(sl[:, 1].sum()) / n_mask
+        return out
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

@@ -36,6 +36,27 @@ def defect_source(source) -> int:
     return int(source)   # (the library checks the range)
 
 
+VH_NORM_MEAN, VH_NORM_P99 = range(2)   # vh_batch_distribution: the divisor of the normalised signal
+VH_DIST_COLS = 8                       # slice_counts columns: mask, defect, LB class 1..6
+_NORM_SOURCES = {"mean": VH_NORM_MEAN, "p99": VH_NORM_P99}
+
+
+def norm_source(norm) -> int:
+    """'mean' | 'p99' or the VH_NORM_* ints -> the int; anything else raises ValueError."""
+    if isinstance(norm, str):
+        if norm not in _NORM_SOURCES:
+            raise ValueError(f"norm is 'mean' or 'p99', got {norm!r}")
+        return _NORM_SOURCES[norm]
+    if isinstance(norm, (bool, float)) or int(norm) != norm:
+        raise ValueError(f"norm is 'mean' or 'p99' or 0..1, got {norm!r}")
+    return int(norm)   # (the library checks the range)
+
+
+def dist_edges(bins, hi):
+    """The histogram's bin edges for display: float64 [bins + 1], arange(bins + 1) * (hi / bins)."""
+    return np.arange(int(bins) + 1) * (float(hi) / int(bins))
+
+
 class N4Params(ct.Structure):
     _fields_ = [("n_levels", ct.c_int32), ("max_iters", ct.c_int32 * 8),
                 ("conv_threshold", ct.c_float), ("ncp", ct.c_int32 * 3),
@@ -115,6 +136,10 @@ _SIGS = {
     "vh_batch_montage_layout": ([_P, _P, _P, _P], ct.c_int),
     "vh_batch_montage": ([_P, _P, _P, _I64], ct.c_int),
     "vh_batch_download_montage": ([_P, _P, _P], ct.c_int),
+    "vh_batch_distribution": ([_P, ct.c_int, ct.c_int32, ct.c_float], ct.c_int),
+    "vh_batch_download_distribution": ([_P, _P, _P, _P], ct.c_int),
+    "vh_distribution": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_float, ct.c_int, ct.c_int32, ct.c_float,
+                         _P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -444,6 +469,26 @@ def defect_map(n4, mask, source, medfilt=1, thresh=0.6, device=0, km=False):
     return (d, bo, cnt, lab) if km else (d, bo, cnt)
 
 
+def distribution(n4, mask, norm="p99", bins=1024, hi=1.5, thresh=0.6, device=0):
+    """The ventilation distribution from host arrays (vh_distribution): the post-N4 chain, then per
+    study the histogram of float32(N4 / d) over the mask (``norm`` 'mean' | 'p99' picks d) and the
+    slice counts of the mask, the run's mean-anchored defect map and the six LB classes.  Returns the
+    dict of Batch.download_distribution.  IndexError for an empty-mask study, like vdp()."""
+    c = context(device)
+    n = as_batch(n4, np.float32)
+    m = as_batch(mask, np.uint8)
+    if n.shape != m.shape:
+        raise ValueError("N4 and mask shapes differ")
+    B, R, C, Z = n.shape
+    bins = int(bins)
+    hist = np.zeros((B, max(bins, 0)), np.uint32)
+    outside = np.zeros((B, 2), np.int64)
+    sl = np.zeros((B, Z, VH_DIST_COLS), np.int64)
+    c.check(c.L.vh_distribution(c.h, _ptr(n), _ptr(m), R, C, Z, B, ct.c_float(thresh), norm_source(norm),
+                                bins, ct.c_float(hi), _ptr(hist), _ptr(outside), _ptr(sl)), "vh_distribution")
+    return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -757,6 +802,29 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_montage(self.h, _ptr(buf), _ptr(status)),
                        "vh_batch_download_montage")
         return montage_views(buf, crop, off, status), status
+
+    def distribution(self, norm="p99", bins=1024, hi=1.5):
+        """Enqueue the ventilation distribution of every study (vh_batch_distribution): the histogram
+        of float32(N4 / d) over mask != 0 in ``bins`` bins of [0, hi) -- d the run's mean anchor
+        (``norm`` 'mean') or 99th percentile ('p99') -- and the per-slice counts of mask, defect and LB
+        class voxels, from the buffers the last run left resident and the defect map as it stands.
+        Read-only; download_distribution fetches the last call's result.  Needs a run."""
+        self.ctx.check(self.L.vh_batch_distribution(self.h, norm_source(norm), int(bins), ct.c_float(hi)),
+                       "vh_batch_distribution")
+        self._dist = (int(bins), float(hi))
+
+    def download_distribution(self):
+        """The last distribution() as a dict: ``hist`` uint32 [B][bins]; ``outside`` int64 [B][2], the
+        masked voxels below 0 and those at or above hi (NaN included); ``slice_counts`` int64
+        [B][Z][8] with columns mask, defect, LB class 1..6; ``edges`` float64 [bins + 1], for display."""
+        bins, hi = getattr(self, "_dist", (0, 1.0))
+        B, _, _, Z = self.shape
+        hist = np.zeros((B, bins), np.uint32)
+        outside = np.zeros((B, 2), np.int64)
+        sl = np.zeros((B, Z, VH_DIST_COLS), np.int64)
+        self.ctx.check(self.L.vh_batch_download_distribution(self.h, _ptr(hist), _ptr(outside), _ptr(sl)),
+                       "vh_batch_download_distribution")
+        return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

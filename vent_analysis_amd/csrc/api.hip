@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <cstdio>
@@ -288,6 +289,7 @@ static void batch_run(vh_batch *b, const vh_run_opts &o, int n4_src) {
     b->mt_layout_valid = false;
     b->ov_valid = false;
     b->mt_valid = false;
+    b->dist_valid = false;
 }
 
 // the study kernel's spin-wait watchdog (n4_study.hip st_spin) leaves N4State.active = -2
@@ -1154,6 +1156,93 @@ int vh_batch_download_montage(vh_batch *b, uint8_t *image, int32_t *status) {
         if (status)
             for (int64_t i = 0; i < b->nb; ++i)
                 status[i] = b->mt_status[i] != VH_OK ? b->mt_status[i] : flag[i] ? VH_ERR_INDEX : VH_OK;
+    })
+}
+
+// ---- the ventilation distribution of a device-resident batch (dist.hip) -------------------------
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_distribution(const vh_batch *b, int norm, int32_t n_bins, float hi) {
+    if (norm != VH_NORM_MEAN && norm != VH_NORM_P99)
+        throw VhError{VH_ERR_ARG, "norm must be VH_NORM_MEAN or VH_NORM_P99"};
+    if (n_bins < 1 || n_bins > VH_COHORT_BINS) throw VhError{VH_ERR_ARG, "n_bins must be 1..1024"};
+    if (!std::isfinite(hi) || !(hi > 0.0f)) throw VhError{VH_ERR_ARG, "hi must be finite and > 0"};
+    if (b && !b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    if (b && !vh_dist_takes(b)) throw VhError{VH_ERR_ARG, "distribution: more than 1900 slices"};
+}
+
+// Enqueue the sweep over what the last run left resident: the N4 volume its chain read, the mask,
+// the LB classes and the defect map as it stands.  It writes its own three buffers only, so nothing
+// another call on the batch reads changes (ci_fresh included).
+static void batch_distribution(vh_batch *b, int norm, int32_t n_bins, float hi) {
+    b->d_dist_hist.reserve((size_t)b->nb * VH_COHORT_BINS);   // the largest n_bins: no regrowth
+    b->d_dist_out.reserve((size_t)b->nb * 2);
+    b->d_dist_sl.reserve((size_t)b->nb * b->Z * VH_DIST_COLS);
+    const float scale = (float)n_bins / hi;   // once, in float32: the kernel multiplies by it
+    vh_dist_launch(b, norm, n_bins, hi, scale);
+    b->dist_bins = n_bins;
+    b->dist_valid = true;
+}
+
+static void batch_download_distribution(vh_batch *b, uint32_t *hist, int64_t *outside, int64_t *slice_counts) {
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (hist)
+        HIP_TRY(hipMemcpyAsync(hist, b->d_dist_hist, sizeof(uint32_t) * nb * b->dist_bins, hipMemcpyDeviceToHost, st));
+    if (outside)
+        HIP_TRY(hipMemcpyAsync(outside, b->d_dist_out, sizeof(int64_t) * nb * 2, hipMemcpyDeviceToHost, st));
+    if (slice_counts)
+        HIP_TRY(hipMemcpyAsync(slice_counts, b->d_dist_sl, sizeof(int64_t) * nb * b->Z * VH_DIST_COLS,
+                               hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_distribution(vh_batch *b, int norm, int32_t n_bins, float hi) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        check_distribution(b, norm, n_bins, hi);
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_distribution(b, norm, n_bins, hi);
+    })
+}
+
+int vh_batch_download_distribution(vh_batch *b, uint32_t *hist, int64_t *outside, int64_t *slice_counts) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!b->dist_valid)
+            throw VhError{VH_ERR_ARG, "vh_batch_distribution has not been called since the last run"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_download_distribution(b, hist, outside, slice_counts);
+    })
+}
+
+int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                    int64_t batch, float thresh, int norm, int32_t n_bins, float hi, uint32_t *hist,
+                    int64_t *outside, int64_t *slice_counts) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!n4 || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_distribution(nullptr, norm, n_bins, hi);
+        HIP_TRY(hipSetDevice(ctx->device));
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        if (!vh_dist_takes(b)) throw VhError{VH_ERR_ARG, "distribution: more than 1900 slices"};
+        const size_t NV = (size_t)batch * b->V;
+        HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
+        batch_upload(b, nullptr, mask);
+        vh_run_opts o;
+        vh_default_run_opts(&o);
+        o.do_n4 = 0;
+        o.do_snr = 0;
+        o.do_kmeans = 0;
+        o.thresh = thresh;
+        o.profile = ctx->profile;
+        batch_run(b, o, 2);
+        batch_distribution(b, norm, n_bins, hi);
+        batch_download_distribution(b, hist, outside, slice_counts);
+        std::vector<VolScalars> sc(batch);
+        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < batch; ++i)
+            if (sc[i].n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
     })
 }
 

@@ -314,6 +314,12 @@ struct vh_batch {
     std::vector<int32_t> mt_status;  // [nb] VH_OK / VH_ERR_EMPTY of the layout
     bool mt_layout_valid = false;    // the layout is the last run's
     bool mt_valid = false;           // vh_batch_montage has been enqueued since the last run
+    // vh_batch_distribution (dist.hip): every buffer on first demand
+    Buf<uint32_t> d_dist_hist;       // [nb][dist_bins] the last call's histograms
+    Buf<unsigned long long> d_dist_out;   // [nb][2] masked voxels below 0 / at or above hi (NaN included)
+    Buf<unsigned long long> d_dist_sl;    // [nb][Z][VH_DIST_COLS] slice counts
+    int32_t dist_bins = 0;           // n_bins of the last vh_batch_distribution
+    bool dist_valid = false;         // vh_batch_distribution has been enqueued since the last run
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -476,6 +482,11 @@ void vh_overlay_launch(hipStream_t s, const float *d_n4, const uint8_t *d_def, i
 // the batch renderings (vh_batch_overlay is vh_overlay_launch on the resident buffers)
 void vh_crop_layout_launch(vh_batch *b);   // -> d_mt_crop, from the last run's mask statistics
 void vh_montage_b_launch(vh_batch *b, bool proton, int64_t prow, bool ci_on);
+// dist.hip: the distribution sweep over the resident N4, mask, defect map and LB classes into
+// d_dist_hist / d_dist_out / d_dist_sl (zeroed first); vh_dist_takes: the slice counters fit in LDS
+#define VH_DIST_MAX_Z 1900
+bool vh_dist_takes(const vh_batch *b);
+void vh_dist_launch(vh_batch *b, int norm, int n_bins, float hi, float scale);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
