@@ -1725,8 +1725,8 @@ static_assert(PC_APASS >= 1 && PC_APASS <= 2, "PC_APASS: 1 or 2 phase-A stages (
 #define PC_XSIG 1   // exact sig after stage 0 (PCX above); 0: stage 1 and the exact rounds always
 #endif
 // PEXP: ld returns p = expf_cr(d) already (the study kernel's eval stored it, ST_EVAL_EXP)
-// pass 0's transpose groups: PC_G0 steps of every block per two barriers (LDS: PC_G0 (NL + 8) floats
-// over the PcShared area, so the area is the larger of the two)
+// pass 0's transpose groups: PC_G0 steps of a wave's 64 blocks per trip (LDS: one tile of PC_G0 rows
+// of 64 + 8 floats per wave over the PcShared area, so the area is the larger of the two)
 #ifndef PC_G0
 #define PC_G0 8
 #endif
@@ -1745,10 +1745,31 @@ static_assert(PC_APASS >= 1 && PC_APASS <= 2, "PC_APASS: 1 or 2 phase-A stages (
 #ifndef PC_INLINE
 #define PC_INLINE 0    // 1: pcw_run inlined (LDS through ds_* instead of flat; A/B builds)
 #endif
+// pcw_run's LoadD: ld(r) returns d at raster rank r.  A load of two dependent stages (the sweep
+// driver reads d through the raster -> compact permutation) also offers index(r) and value(index):
+// pass 0 then issues a group's index loads together and its value loads together (two round trips
+// per group, not one pair per load).
+struct PcPermLoad {
+    const float *D;
+    const int32_t *perm;
+    __device__ __forceinline__ int32_t index(int64_t r) const { return perm[r]; }
+    __device__ __forceinline__ float value(int32_t i) const { return D[i]; }
+    __device__ __forceinline__ float operator()(int64_t r) const { return D[perm[r]]; }
+};
+template <class L>
+__device__ __forceinline__ auto pc_ld_index(const L &ld, int64_t r, int) -> decltype(ld.index(r)) { return ld.index(r); }
+template <class L>
+__device__ __forceinline__ int64_t pc_ld_index(const L &, int64_t r, long) { return r; }
+template <class L, class I>
+__device__ __forceinline__ auto pc_ld_value(const L &ld, I i, int) -> decltype(ld.value(i)) { return ld.value(i); }
+template <class L, class I>
+__device__ __forceinline__ float pc_ld_value(const L &ld, I r, long) { return ld(r); }
+#define PC_P0W (64 + 8)   // floats per row of a wave's pass-0 tile (8 of padding: bank conflicts)
 template <int NL>
 __host__ __device__ constexpr size_t pcw_lds_bytes() {
-    return sizeof(PcShared<NL>) > sizeof(float) * PC_G0 * (NL + 8) ? sizeof(PcShared<NL>)
-                                                                    : sizeof(float) * PC_G0 * (NL + 8);
+    return sizeof(PcShared<NL>) > sizeof(float) * PC_G0 * PC_P0W * (NL / 64)
+               ? sizeof(PcShared<NL>)
+               : sizeof(float) * PC_G0 * PC_P0W * (NL / 64);
 }
 #if PC_INLINE
 #define PCW_INL __forceinline__
@@ -1773,13 +1794,20 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
 #endif
     // pass 0: p = exp(d) from raster order into block layout (P[s NL + j]) and the block sums.  A
     // block's d values are consecutive in raster order, so one thread reading its own block touched
-    // 64 cache lines per wave-wide load; instead the workgroup loads each group of PC_G0 steps of
-    // all blocks together (8 lanes per block: 32-byte runs) and transposes it through LDS (the
-    // PcShared area, rewritten after this pass; rows padded by 8 floats against bank conflicts).
-    constexpr int G0 = PC_G0, TS = NL + 8;
-    static_assert(sizeof(float) * G0 * TS <= pcw_lds_bytes<NL>(), "pass-0 transpose buffer");
-    float *const T0 = reinterpret_cast<float *>(&S);
-    const uint32_t lmax = m.L + (m.rem ? 1u : 0u);
+    // 64 cache lines per wave-wide load; instead each group of PC_G0 steps of 64 blocks is loaded
+    // together (8 lanes per block: 32-byte runs) and transposed through LDS (the PcShared area,
+    // rewritten after this pass; rows padded by 8 floats against bank conflicts).
+    // Each wave transposes its own 64 blocks (j = 64 w .. 64 w + 63: consecutive in raster order)
+    // through a tile of its own, so the loop below has no workgroup barrier: the waves drift, one
+    // wave's exp over another's loads, and a wave runs only as many groups as its own blocks need.
+    constexpr int G0 = PC_G0, TS = PC_P0W, BQ = 64 / G0;
+    static_assert(64 % G0 == 0 && NL % 64 == 0, "pass 0: G0 lanes per block, whole waves");
+    static_assert(sizeof(float) * G0 * TS * (NL / 64) <= pcw_lds_bytes<NL>(), "pass-0 transpose tiles");
+    // (wave-uniform values through readfirstlane: the loop below then branches on scalars)
+    const uint32_t lane = (uint32_t)tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+    float *const T0 = reinterpret_cast<float *>(&S) + wv * (uint32_t)(G0 * TS);
+    // block lengths never increase with j: the wave's first block is its longest (0: nothing to do)
+    const uint32_t lmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc_len(m, 64u * wv));
     // s1 = sum of (p - 1) in double: exact wherever the early decision uses it (it requires every p
     // in (0.5, 1.9): then p - 1 is a multiple of 2^-24 with |p - 1| < 0.9, so it and every partial
     // sum of n < 2^24 of them are integers times 2^-24 below 2^24 in size -- at most 48 significant
@@ -1795,8 +1823,19 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
     // min p + N0 h] lies inside every step's [p - N h, p + N h] -- the intersection the
     // certification needs, at 2 float ops per step instead of 10 double ones
     float pmax = -__int_as_float(0x7f800000), pmin = __int_as_float(0x7f800000);
-    // thread tid loads step i = tid % G0 of blocks tid / G0 + (NL / G0) q; the next group's
-    // loads are in flight while this group's exp runs
+    // lane l loads step g0 + l % G0 of the wave's blocks 64 w + l / G0 + (64 / G0) q; the next
+    // group's loads are in flight while this group's exp runs.  Per block, fixed over the trips:
+    // the raster rank of its first step (rb) and the last rank a load of it may touch (re: the
+    // block's last step, clamped to n - 1 in 64 bits; 0 for an empty block beside a non-empty one)
+    const uint32_t li = lane % G0;
+    uint32_t rb[G0], re[G0];
+#pragma unroll
+    for (int q = 0; q < G0; ++q) {
+        const uint32_t jb = 64u * wv + lane / G0 + (uint32_t)BQ * q, lb = pc_len(m, jb);
+        const int64_t last = lb ? (int64_t)(pc_k0(m, jb) - 1u + (lb - 1u)) : 0;
+        rb[q] = lb ? pc_k0(m, jb) - 1u + li : 0u;
+        re[q] = (uint32_t)(last < n ? last : (n > 0 ? n - 1 : 0));
+    }
     float v[G0];
     auto fetch = [&](uint32_t g0) {
 #if PC_P0CLAMP
@@ -1804,41 +1843,55 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
         // `in ? ld(...) : 0` compiled to an exec-masked branch per load whose s_waitcnt vmcnt(0)
         // waited for each load before the next issued -- the group's 8 loads one round trip at a
         // time (scripts/dev/isa_serial_loads.py)
+        // (a two-stage ld, PcPermLoad: the 8 index loads first, then the 8 value loads)
+        decltype(pc_ld_index(ld, (int64_t)0, 0)) ix[G0];
 #pragma unroll
         for (int q = 0; q < G0; ++q) {   // (the value of a step past the block's end: never read)
-            const uint32_t jb = (uint32_t)tid / G0 + (uint32_t)(NL / G0) * q, i = (uint32_t)tid % G0;
-            const uint32_t lb = pc_len(m, jb), ii = g0 + i;
-            const int64_t r = lb ? (int64_t)(pc_k0(m, jb) - 1u + (ii < lb ? ii : lb - 1u)) : 0;
-            v[q] = ld(r < n ? r : (n > 0 ? n - 1 : 0));
+            const uint32_t r = rb[q] + g0;
+            ix[q] = pc_ld_index(ld, (int64_t)(r < re[q] ? r : re[q]), 0);
         }
+        // (the scheduler otherwise starts on the first index's address before the last index load
+        // has issued, and the wait for it splits the index loads 7 + 1: a third round trip)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < G0; ++q) v[q] = pc_ld_value(ld, ix[q], 0);
 #else
 #pragma unroll
         for (int q = 0; q < G0; ++q) {
-            const uint32_t jb = (uint32_t)tid / G0 + (uint32_t)(NL / G0) * q, i = (uint32_t)tid % G0;
-            v[q] = g0 + i < pc_len(m, jb) ? ld((int64_t)(pc_k0(m, jb) - 1u + g0 + i)) : 0.0f;
+            const uint32_t jb = 64u * wv + lane / G0 + (uint32_t)BQ * q;
+            v[q] = g0 + li < pc_len(m, jb) ? ld((int64_t)(pc_k0(m, jb) - 1u + g0 + li)) : 0.0f;
         }
 #endif
     };
     // (n == 0: no load at all -- the clamped index 0 would read a permutation entry of an empty
-    // study, r6y's illegal address)
+    // study, r6y's illegal address; a wave whose blocks are all empty loads nothing either)
     if (lmax) fetch(0);
 #ifdef PC_PROF
-    unsigned long long p0t[4] = {0, 0, 0, 0}, p0c = clock64();
+    unsigned long long p0t[3] = {0, 0, 0}, p0c = clock64();
 #define P0M(k) do { const unsigned long long _c = clock64(); p0t[k] += _c - p0c; p0c = _c; } while (0)
 #else
 #define P0M(k) do { } while (0)
 #endif
+    // No __syncthreads() in this loop: its trip count is the wave's own.  Within the wave the LDS
+    // operations execute in order; the wavefront-scope fences keep the compiler from moving a
+    // lane's tile reads over another lane's writes (and the next group's writes over the reads).
+    // (LLVM's AMDGPU memory model, "Memory Model" code sequences: at wavefront scope a fence needs
+    // no s_waitcnt, since one wave's memory operations of a kind complete in issue order; so the
+    // fences emit no instruction and only bind the compiler.)
     for (uint32_t g0 = 0; g0 < lmax; g0 += G0) {
 #pragma unroll
-        for (int q = 0; q < G0; ++q)
-            lds_st(T0 + (tid % G0) * TS + tid / G0 + (NL / G0) * q, v[q]);
+        for (int q = 0; q < G0; ++q) lds_st(T0 + li * TS + lane / G0 + BQ * q, v[q]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         P0M(0);   // (profiling) the group's loads arrived and went to LDS
-        __syncthreads();
-        P0M(1);   // first barrier
         if (g0 + G0 < lmax) fetch(g0 + G0);
         float tv[G0];   // this group's steps of this thread's block, from LDS (ds_read: lgkmcnt only)
 #pragma unroll
-        for (int i = 0; i < G0; ++i) tv[i] = lds_ld(T0 + i * TS + j);
+        for (int i = 0; i < G0; ++i) tv[i] = lds_ld(T0 + i * TS + lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int i = 0; i < G0; ++i)
             if (g0 + i < len) {
@@ -1859,15 +1912,13 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
                 pmax = fmaxf(pmax, p);
                 pmin = fminf(pmin, p);
             }
-        P0M(2);   // exp, stores and sums
-        __syncthreads();
-        P0M(3);   // second barrier
+        P0M(1);   // exp, stores and sums
     }
-#undef P0M
-#ifdef PC_PROF
-    if (blockIdx.x == 0 && tid == 0)
-        printf("PCW_P0 loads %llu bar1 %llu work %llu bar2 %llu\n", p0t[0], p0t[1], p0t[2], p0t[3]);
-#endif
+    // The tiles overlay PcShared: every wave has read its last tile before any field is written.
+    // (The only workgroup barrier of pass 0; it is outside every wave-dependent branch.)
+    __syncthreads();
+    P0M(2);   // the wait for the slowest wave
+#undef P0M   // (the PCW_P0 lines are printed at the end of the call: a printf here would sit in c1 - c0)
     if (tid == 0) {   // flags from an earlier call (or other phases' use of this LDS) must not match
         S.done = 0;
         S.fallback = 0;
@@ -1878,6 +1929,7 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
     }
 #ifdef PC_PROF
     if (tid < 32) S.pchg[tid] = S.pwav[tid] = 0;
+    if (tid == 0) S.xwcyc = S.xscyc = 0;   // (the tiles lay over them; a call without PCX prints them)
 #endif
     S.s1(j) = (double)s1;
     S.s2(j) = (double)s2;
@@ -2167,6 +2219,10 @@ __device__ PCW_INL void pcw_run(LoadD ld, float *P, int64_t n, PcShared<NL> &S,
         if (blockIdx.x == 0 && xs) printf("PCW_X scan %llu walks %llu\n", S.xscyc, S.xwcyc);
 #endif
     }
+#ifdef PC_PROF   // pass 0 of the first and the last wave: its own loop, then the wait for the slowest
+    if (blockIdx.x == 0 && lane == 0 && (wv == 0 || wv == NL / 64 - 1))
+        printf("PCW_P0 wave %u loads %llu work %llu bar %llu\n", wv, p0t[0], p0t[1], p0t[2]);
+#endif
 }
 
 
