@@ -40,6 +40,10 @@
  *                Vent_Analysis.py:1019-1026), all six linear-binning class counts (:256; the reference
  *                reports classes 1+2 only, :257) and the slice-wise mask / defect counts, per study from
  *                the resident buffers (build-defined); kernel-timing class "dist_b", not listed either
+ *   vh_batch_noise_sigma / vh_batch_denoise / vh_batch_download_hp / vh_noise_sigma / vh_denoise
+ *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
+ *                non-local-means filter of the resident HPvent, specified to the last bit, and the
+ *                noise estimate it needs (build-defined); kernel-timing class "denoise_b", not listed
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -346,6 +350,59 @@ int vh_batch_download_distribution(vh_batch *b, uint32_t *hist /* [nb][n_bins] *
 int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
                     int64_t batch, float thresh, int norm, int32_t n_bins, float hi,
                     uint32_t *hist, int64_t *outside, int64_t *slice_counts);
+
+/* ---- the denoise option of a device-resident batch ("Denoise Option", Vent_Analysis.py:1025) -------
+ * An in-plane non-local-means filter of the resident HPvent with a Tukey bisquare weight.  Every
+ * operation is a correctly-rounded float32 add, subtract, multiply, divide or square root in a fixed
+ * order (no fused multiply-add), so the result is specified to the last bit (tests/denoise_ref.py is
+ * the same arithmetic in numpy).
+ *
+ * The filter, for one study x (float32 [R][C][Z], the slice axis fastest), every slice on its own
+ * (slices are 10 mm thick against 1.5 mm pixels: a 3-D patch would mix unrelated anatomy).
+ * Parameters: search radius S = search_r (1..5), patch radius P = patch_r (0..2), strength k (a
+ * float32), the study's noise sigma (float32, finite, > 0), rician (0: off, else on).  Once per study,
+ * in double and then rounded to float32: n = (2P+1)^2, inv_h2 = float32(1 / (2 n (k sigma)^2)),
+ * bias = float32(2 sigma^2).  Indices outside the slice are clamped: X(r, c) stands for
+ * x[clamp(r, 0, R-1)][clamp(c, 0, C-1)][z], which is np.pad(x, mode='edge') by S + P.
+ * For every voxel (r, c, z) the search offsets (dr, dc) run in raster order, dr outer, each from -S
+ * to S, with num = den = +0 at the start.  For each offset:
+ *   d2 = +0; for the patch offsets (ur, uc) in raster order, ur outer, each from -P to P:
+ *       t = X(r+ur, c+uc) - X(r+dr+ur, c+dc+uc);  d2 = d2 + t*t   (multiply and add rounded separately)
+ *   u = d2 * inv_h2
+ *   w = (u < 1) ? (1-u)*(1-u) : 0      the bisquare weight: compact support, so a dissimilar patch
+ *                                      weighs exactly 0, and no exp whose rounding a library decides
+ *   num = num + w * Y(r+dr, c+dc);  den = den + w      Y = X, or Y = X*X with rician
+ * out = num / den (IEEE float32 division; the centre offset has w = 1, so den >= 1 for finite input);
+ * with rician v = out - bias, then out = v > 0 ? sqrtf(v) : 0.  Non-finite input voxels follow the
+ * same pointwise rules: nothing special-cases them.
+ *
+ * The noise estimate: sigma = float32(sqrt(S2 / (2 N))), S2 and N the sum of squares (double) and the
+ * count over exactly the voxels calculate_SNR counts as noise (the noise box of Vent_Analysis.py:340-351
+ * with its quirks, as vh_snr has it): the Rayleigh maximum-likelihood estimate of a magnitude image's
+ * background.  The device sums the doubles in its own fixed order, so against another order the
+ * float32 may differ by one ulp.  NaN for a study whose SNR is undefined (no masked column > 0, or
+ * no noise voxel).
+ *
+ * vh_batch_noise_sigma, after vh_batch_upload: the mask statistics and the SNR sweep on the resident
+ * HPvent, then waits.  vh_batch_denoise enqueues only: it replaces the resident HPvent with its
+ * denoised volume, so the next vh_batch_run (N4, SNR, the VDP chain, the montage's HPvent panel) sees
+ * it.  VH_ERR_ARG, with nothing enqueued: a null batch or sigma, search_r outside 1..5, patch_r
+ * outside 0..2, a strength that is not finite or <= 0, any sigma that is not finite or <= 0 (and a
+ * batch of more than 65535 studies).  Called after a run, either of the two puts the batch back where
+ * vh_batch_upload left it (the first rewrites the mask statistics, the second the volume the results
+ * came from): the calls that need a run return VH_ERR_ARG until the next one.  vh_batch_download_hp
+ * waits and returns the resident HPvent as it stands.  The filter's kernel-timing class is "denoise_b"
+ * (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * vh_noise_sigma and vh_denoise are the host-buffer forms on the context's scratch batch. */
+int vh_batch_noise_sigma(vh_batch *b, float *sigma /* [nb] */);
+int vh_batch_denoise(vh_batch *b, const float *sigma /* [nb] */, float strength, int search_r, int patch_r,
+                     int rician);
+int vh_batch_download_hp(vh_batch *b, float *hp /* [nb][R][C][Z] */);
+int vh_noise_sigma(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                   int64_t batch, float *sigma);
+int vh_denoise(vh_ctx *ctx, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
+               const float *sigma, float strength, int search_r, int patch_r, int rician, float *out);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

@@ -283,6 +283,30 @@ class Vent_Analysis:
             out['vdp_from_slices'] = 100 * np.float64(sl[:, 1].sum()) / n_mask
         return out
 
+    def estimate_noise(self, A=None):
+        """The noise sigma of ``A`` (default ``self.HPvent``) for denoise (build-defined): float32
+        sqrt(sum(A^2) / (2 N)) over the voxels calculate_SNR counts as noise for ``self.mask`` -- the
+        Rayleigh maximum-likelihood estimate of a magnitude image's background -- on the GPU.  NaN
+        where calculate_SNR is undefined.  Returns the value and sets nothing on the object."""
+        m, _ = _mask_value(self.mask)
+        A = self.HPvent if A is None else A
+        return _lib.noise_sigma(np.asarray(A, dtype=np.float32), m, device=self.device)[0]
+
+    def denoise(self, A=None, strength=2.0, search=3, patch=1, rician=False, sigma=None):
+        """The "Denoise Option" of the reference's list (build-defined): the in-plane non-local-means
+        filter of ``A`` (default ``self.HPvent``) on the GPU, with a bisquare weight over patches of
+        radius ``patch`` within ``search`` pixels, bandwidth ``strength`` * sigma; ``rician`` filters
+        the squared image and removes the 2 sigma^2 bias.  ``sigma`` None takes estimate_noise(A) and
+        raises ValueError if that is NaN.  Returns the float32 volume and sets nothing on the object:
+        to turn the option on, assign it (``va.HPvent = va.denoise()``) before calculate_VDP."""
+        A = np.asarray(self.HPvent if A is None else A, dtype=np.float32)
+        if sigma is None:
+            sigma = self.estimate_noise(A)
+            if np.isnan(sigma):
+                raise ValueError("denoise: the noise estimate is undefined for this mask; pass sigma")
+        return _lib.denoise(A, sigma, strength=strength, search=search, patch=patch, rician=rician,
+                            device=self.device)[0]
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

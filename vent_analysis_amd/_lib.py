@@ -57,6 +57,17 @@ def dist_edges(bins, hi):
     return np.arange(int(bins) + 1) * (float(hi) / int(bins))
 
 
+def denoise_constants(sigma, strength=2.0, patch=1):
+    """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
+    sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
+    2 sigma^2."""
+    s, k = np.float64(np.float32(sigma)), np.float64(np.float32(strength))
+    ks = k * s
+    with np.errstate(divide="ignore", over="ignore"):
+        return (np.float32(np.float64(1.0) / (2.0 * np.float64((2 * int(patch) + 1) ** 2) * (ks * ks))),
+                np.float32(2.0 * (s * s)))
+
+
 class N4Params(ct.Structure):
     _fields_ = [("n_levels", ct.c_int32), ("max_iters", ct.c_int32 * 8),
                 ("conv_threshold", ct.c_float), ("ncp", ct.c_int32 * 3),
@@ -140,6 +151,11 @@ _SIGS = {
     "vh_batch_download_distribution": ([_P, _P, _P, _P], ct.c_int),
     "vh_distribution": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_float, ct.c_int, ct.c_int32, ct.c_float,
                          _P, _P, _P], ct.c_int),
+    "vh_batch_noise_sigma": ([_P, _P], ct.c_int),
+    "vh_batch_denoise": ([_P, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int], ct.c_int),
+    "vh_batch_download_hp": ([_P, _P], ct.c_int),
+    "vh_noise_sigma": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P], ct.c_int),
+    "vh_denoise": ([_P, _P, _I64, _I64, _I64, _I64, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -489,6 +505,51 @@ def distribution(n4, mask, norm="p99", bins=1024, hi=1.5, thresh=0.6, device=0):
     return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
 
 
+def _denoise_args(sigma, n, strength, search, patch):
+    """The per-study sigma as float32 [n] (a scalar is repeated) and the checked ints; ValueError for
+    what the library would refuse, so the message names the argument."""
+    sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float32), (n,)))
+    if not (np.isfinite(sg).all() and (sg > 0).all()):
+        raise ValueError(f"denoise: every sigma must be finite and > 0, got {sg}")
+    if isinstance(search, (bool, float)) or isinstance(patch, (bool, float)):
+        raise ValueError("denoise: search and patch are ints")
+    if not 1 <= int(search) <= 5:
+        raise ValueError(f"denoise: search must be 1..5, got {search!r}")
+    if not 0 <= int(patch) <= 2:
+        raise ValueError(f"denoise: patch must be 0..2, got {patch!r}")
+    if not (np.isfinite(np.float32(strength)) and np.float32(strength) > 0):
+        raise ValueError(f"denoise: strength must be finite and > 0, got {strength!r}")
+    return sg, int(search), int(patch)
+
+
+def noise_sigma(hp, mask, device=0):
+    """The noise of each study from host arrays (vh_noise_sigma): float32 [B], sqrt(S2 / (2 N)) over
+    the voxels calculate_SNR counts as noise (the Rayleigh maximum-likelihood estimate of a magnitude
+    background); NaN where the SNR is undefined."""
+    c = context(device)
+    h = as_batch(hp, np.float32)
+    m = as_batch(mask, np.uint8)
+    if h.shape != m.shape:
+        raise ValueError("HPvent and mask shapes differ")
+    B, R, C, Z = h.shape
+    out = np.zeros(B, np.float32)
+    c.check(c.L.vh_noise_sigma(c.h, _ptr(h), _ptr(m), R, C, Z, B, _ptr(out)), "vh_noise_sigma")
+    return out
+
+
+def denoise(hp, sigma, strength=2.0, search=3, patch=1, rician=False, device=0):
+    """The in-plane non-local-means filter from host arrays (vh_denoise; the spec is in
+    include/vent_hip.h): ``sigma`` a scalar or one value per study.  Returns float32 [B][R][C][Z]."""
+    c = context(device)
+    h = as_batch(hp, np.float32)
+    B, R, C, Z = h.shape
+    sg, search, patch = _denoise_args(sigma, B, strength, search, patch)
+    out = np.empty_like(h)
+    c.check(c.L.vh_denoise(c.h, _ptr(h), R, C, Z, B, _ptr(sg), ct.c_float(strength), search, patch,
+                           int(bool(rician)), _ptr(out)), "vh_denoise")
+    return out
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -825,6 +886,36 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_distribution(self.h, _ptr(hist), _ptr(outside), _ptr(sl)),
                        "vh_batch_download_distribution")
         return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
+
+    def noise_sigma(self):
+        """float32 [B]: the noise of each resident HPvent (vh_batch_noise_sigma), sqrt(S2 / (2 N))
+        over the voxels calculate_SNR counts as noise; NaN where the SNR is undefined.  Call it after
+        upload (after a run it discards the run's results, like denoise)."""
+        out = np.zeros(self.shape[0], np.float32)
+        self.ctx.check(self.L.vh_batch_noise_sigma(self.h, _ptr(out)), "vh_batch_noise_sigma")
+        return out
+
+    def denoise(self, sigma=None, strength=2.0, search=3, patch=1, rician=False):
+        """Enqueue the in-plane non-local-means filter (vh_batch_denoise; the spec is in
+        include/vent_hip.h): the resident HPvent becomes its denoised volume, which the next run()
+        reads.  ``sigma`` is a scalar or one value per study; None estimates it with noise_sigma()
+        first and raises ValueError if the estimate is NaN for any study.  Returns the sigma used,
+        float32 [B].  After a run, the calls that need a run raise ValueError until the next one."""
+        if sigma is None:
+            sigma = self.noise_sigma()
+            if np.isnan(sigma).any():
+                raise ValueError(f"denoise: the noise estimate is undefined for studies "
+                                 f"{np.flatnonzero(np.isnan(sigma)).tolist()}; pass sigma")
+        sg, search, patch = _denoise_args(sigma, self.shape[0], strength, search, patch)
+        self.ctx.check(self.L.vh_batch_denoise(self.h, _ptr(sg), ct.c_float(strength), search, patch,
+                                               int(bool(rician))), "vh_batch_denoise")
+        return sg
+
+    def download_hp(self):
+        """The resident HPvent as it stands (vh_batch_download_hp), float32 [B][R][C][Z]."""
+        out = np.empty(self.shape, np.float32)
+        self.ctx.check(self.L.vh_batch_download_hp(self.h, _ptr(out)), "vh_batch_download_hp")
+        return out
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

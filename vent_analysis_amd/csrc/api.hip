@@ -1246,6 +1246,123 @@ int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R
     })
 }
 
+// ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------
+// back where vh_batch_upload leaves a batch: the resident HPvent or the mask statistics and scalars
+// are no longer the last run's, so the calls that read a run's results refuse until the next one
+static void batch_forget_run(vh_batch *b) {
+    b->have_result = false;
+    b->d_n4_last = nullptr;
+    b->km_valid = false;
+    b->sel_valid = false;
+    b->ci_fresh = false;
+    b->mt_layout_valid = false;
+    b->ov_valid = false;
+    b->mt_valid = false;
+    b->dist_valid = false;
+}
+
+// the mask statistics and the SNR sweep of the resident HPvent, then the Rayleigh estimate of every
+// study from the sweep's noise partials; waits
+static void batch_noise_sigma(vh_batch *b, float *sigma) {
+    b->d_dn_sigma.reserve((size_t)b->nb);
+    vh_launch_mask_stats(b);   // (rewrites the scalars: a run's results are gone)
+    batch_forget_run(b);
+    vh_launch_snr(b);
+    vh_noise_sigma_launch(b, b->d_dn_sigma);
+    d2h_on_stream(b, sigma, b->d_dn_sigma, sizeof(float) * (size_t)b->nb);
+}
+
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_denoise(const float *sigma, int64_t nb, float strength, int search_r, int patch_r) {
+    if (!sigma) throw VhError{VH_ERR_ARG, "null sigma"};
+    if (search_r < 1 || search_r > 5) throw VhError{VH_ERR_ARG, "search_r must be 1..5"};
+    if (patch_r < 0 || patch_r > 2) throw VhError{VH_ERR_ARG, "patch_r must be 0..2"};
+    if (!std::isfinite(strength) || !(strength > 0.0f))
+        throw VhError{VH_ERR_ARG, "strength must be finite and > 0"};
+    for (int64_t i = 0; i < nb; ++i)
+        if (!std::isfinite(sigma[i]) || !(sigma[i] > 0.0f))
+            throw VhError{VH_ERR_ARG, "every sigma must be finite and > 0 (study " + std::to_string(i) + ")"};
+}
+
+// Enqueue the filter from d_hp into d_n4 (free until the next run writes it) and exchange the two
+// buffers: the denoised volumes are the resident HPvent from here on.  Every launch takes the
+// buffers' addresses when it is enqueued, on this one stream, so the exchange is safe behind work
+// still in flight.
+static void batch_denoise(vh_batch *b, const float *sigma, float strength, int search_r, int patch_r, int rician) {
+    if (!vh_denoise_takes(b)) throw VhError{VH_ERR_ARG, "denoise: batch or tile count out of range"};
+    const double n = (double)((2 * patch_r + 1) * (2 * patch_r + 1));
+    std::vector<float> prm(2 * (size_t)b->nb);
+    for (int64_t i = 0; i < b->nb; ++i) {   // in double, rounded to float32 once
+        const double ks = (double)strength * (double)sigma[i];
+        prm[2 * i] = (float)(1.0 / (2.0 * n * (ks * ks)));
+        prm[2 * i + 1] = (float)(2.0 * ((double)sigma[i] * (double)sigma[i]));
+    }
+    b->d_dn_prm.reserve(prm.size());
+    // (pageable source: the copy has left prm when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_dn_prm, prm.data(), sizeof(float) * prm.size(), hipMemcpyHostToDevice, b->stream));
+    vh_denoise_launch(b, b->d_hp, b->d_n4, b->d_dn_prm, search_r, patch_r, rician);
+    std::swap(b->d_hp, b->d_n4);
+    batch_forget_run(b);
+}
+
+int vh_batch_noise_sigma(vh_batch *b, float *sigma) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!sigma) throw VhError{VH_ERR_ARG, "null buffer"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_noise_sigma(b, sigma);
+    })
+}
+
+int vh_batch_denoise(vh_batch *b, const float *sigma, float strength, int search_r, int patch_r, int rician) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        check_denoise(sigma, b->nb, strength, search_r, patch_r);
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_denoise(b, sigma, strength, search_r, patch_r, rician);
+    })
+}
+
+int vh_batch_download_hp(vh_batch *b, float *hp) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!hp) throw VhError{VH_ERR_ARG, "null buffer"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        d2h_on_stream(b, hp, b->d_hp, sizeof(float) * (size_t)b->nb * b->V);
+    })
+}
+
+int vh_noise_sigma(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
+                   int64_t batch, float *sigma) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!hp || !mask || !sigma) throw VhError{VH_ERR_ARG, "null buffer"};
+        HIP_TRY(hipSetDevice(ctx->device));
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, hp, mask);
+        batch_noise_sigma(b, sigma);
+    })
+}
+
+int vh_denoise(vh_ctx *ctx, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
+               const float *sigma, float strength, int search_r, int patch_r, int rician, float *out) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!hp || !out) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_denoise(sigma, batch, strength, search_r, patch_r);
+        HIP_TRY(hipSetDevice(ctx->device));
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, hp, nullptr);
+        batch_denoise(b, sigma, strength, search_r, patch_r, rician);
+        d2h_on_stream(b, out, b->d_hp, sizeof(float) * (size_t)batch * b->V);
+    })
+}
+
 // ---- TWIX recon (recon.hip) -------------------------------------------------------------------
 int vh_recon(vh_ctx *ctx, const double *k, int64_t n0, int64_t n1, int64_t nz, double *out) {
     API_TRY(ctx, {

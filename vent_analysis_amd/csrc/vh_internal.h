@@ -320,6 +320,9 @@ struct vh_batch {
     Buf<unsigned long long> d_dist_sl;    // [nb][Z][VH_DIST_COLS] slice counts
     int32_t dist_bins = 0;           // n_bins of the last vh_batch_distribution
     bool dist_valid = false;         // vh_batch_distribution has been enqueued since the last run
+    // vh_batch_denoise / vh_batch_noise_sigma (denoise.hip): on first demand
+    Buf<float> d_dn_prm;             // [nb][2] the last denoise's inv_h2 and bias of each study
+    Buf<float> d_dn_sigma;           // [nb] the last noise estimate
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -487,6 +490,12 @@ void vh_montage_b_launch(vh_batch *b, bool proton, int64_t prow, bool ci_on);
 #define VH_DIST_MAX_Z 1900
 bool vh_dist_takes(const vh_batch *b);
 void vh_dist_launch(vh_batch *b, int norm, int n_bins, float hi, float scale);
+// denoise.hip: the non-local-means filter of every study, src -> dst (two volumes of the batch), with
+// d_prm [nb][2] = inv_h2, bias; vh_denoise_takes: the grid fits.  vh_noise_sigma_launch: d_snrpart
+// (after vh_launch_snr) -> d_sigma [nb]
+bool vh_denoise_takes(const vh_batch *b);
+void vh_denoise_launch(vh_batch *b, const float *src, float *dst, const float *d_prm, int S, int P, int rician);
+void vh_noise_sigma_launch(vh_batch *b, float *d_sigma);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
