@@ -44,6 +44,11 @@
  *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
  *                non-local-means filter of the resident HPvent, specified to the last bit, and the
  *                noise estimate it needs (build-defined); kernel-timing class "denoise_b", not listed
+ *   vh_batch_edit_mask / vh_batch_paint_mask / vh_batch_download_mask / vh_edit_mask
+ *                the "edit mask" item of the reference's list (Vent_Analysis.py:1023): per-slice disc
+ *                erosion, dilation, opening and closing of the resident masks, paint strokes, and the
+ *                mask read back with its voxel count (build-defined); kernel-timing class
+ *                "mask_edit_b", not listed
  *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -403,6 +408,57 @@ int vh_noise_sigma(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R,
                    int64_t batch, float *sigma);
 int vh_denoise(vh_ctx *ctx, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
                const float *sigma, float strength, int search_r, int patch_r, int rician, float *out);
+
+/* ---- editing the masks of a device-resident batch ("edit mask", Vent_Analysis.py:1023) -------------
+ * Disc morphology and paint strokes on the resident mask, in place.  All arithmetic is on bits, so
+ * the result is specified exactly (tests/mask_edit_ref.py is the same in numpy).
+ *
+ * For one study, s(r, c, z) = (mask[r][c][z] != 0).  Every slice is processed on its own (slices are
+ * 10 mm thick against 1.5 mm pixels, as for the denoise filter).  The structuring element of radius k
+ * (1..5) is the disc D_k = {(dr, dc) : dr^2 + dc^2 <= k^2}, of 5, 13, 29, 49, 81 offsets.
+ *   dilate_k:  out(r, c, z) = OR over D_k of s(r + dr, c + dc, z), a position outside the slice
+ *              counting as 0
+ *   erode_k:   out = AND over D_k of s(r + dr, c + dc, z), a position outside the slice counting as 1,
+ *              so the image edge never erodes a mask
+ *   open_k  = dilate_k(erode_k(s))          close_k = erode_k(dilate_k(s))
+ * With these pads open_k(s) is inside s, s inside close_k(s), and both are idempotent.  The
+ * intermediate of open and close is defined on the slice only, and the second step pads it with its
+ * own pad value: it is not computed from a padded input.  These are
+ * scipy.ndimage.binary_dilation(s, structure=disc[:, :, None]) and binary_erosion(..., border_value=1).
+ * Output bytes are 0 / 1.  radius is per study, each 0..5: a study of radius 0 keeps its mask byte for
+ * byte (a 0/255 mask stays 0/255), which is how one study of a batch is edited alone.
+ *
+ * Paint: with p = (strokes != 0) the mask becomes s | p (VH_PAINT_OR), s & ~p (VH_PAINT_ANDNOT), s & p
+ * (VH_PAINT_AND) or s ^ p (VH_PAINT_XOR), written as 0 / 1 bytes for every study.
+ *
+ * vh_batch_edit_mask enqueues only; vh_batch_paint_mask returns once the strokes have left the
+ * caller's buffer (it waits for the work enqueued before it, not for its own kernel).  Both replace the
+ * resident mask, so the next vh_batch_run (the mask statistics, N4, the VDP chain, the SNR noise box,
+ * the montage's crop and mask border) sees the edited one, and both put the batch back where
+ * vh_batch_upload left it, exactly as vh_batch_denoise does: the calls that need a run return
+ * VH_ERR_ARG until the next one.  radius and strokes may be reused as soon as the call returns.  The
+ * resident HPvent, N4 and defect maps are not touched: a map given by vh_batch_set_defect survives.
+ * VH_ERR_ARG, with nothing enqueued: a null batch, radius or strokes, op or how out of range, any
+ * radius outside 0..5 (and a batch of more than 65535 studies).  The kernel-timing class is
+ * "mask_edit_b" (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * vh_batch_download_mask waits and returns the resident mask as it stands -- after an upload, an edit
+ * or a run -- and count[i], the voxels != 0 of study i, counted on the device when asked for (an exact
+ * integer).  vh_edit_mask is the host-buffer form of vh_batch_edit_mask on the context's scratch
+ * batch; out and count are nullable. */
+#define VH_MASK_ERODE 0
+#define VH_MASK_DILATE 1
+#define VH_MASK_OPEN 2
+#define VH_MASK_CLOSE 3
+#define VH_PAINT_OR 0
+#define VH_PAINT_ANDNOT 1
+#define VH_PAINT_AND 2
+#define VH_PAINT_XOR 3
+int vh_batch_edit_mask(vh_batch *b, int op, const int32_t *radius /* [nb] */);
+int vh_batch_paint_mask(vh_batch *b, const uint8_t *strokes /* [nb][V] */, int how);
+int vh_batch_download_mask(vh_batch *b, uint8_t *mask /* [nb][V] */, int64_t *count /* [nb] */);  /* both nullable */
+int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                 int op, const int32_t *radius, uint8_t *out, int64_t *count);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

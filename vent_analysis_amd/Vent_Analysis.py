@@ -307,6 +307,33 @@ class Vent_Analysis:
         return _lib.denoise(A, sigma, strength=strength, search=search, patch=patch, rician=rician,
                             device=self.device)[0]
 
+    def edit_mask(self, op=None, radius=1, strokes=None, how='or'):
+        """The "edit mask" item of the reference's list (build-defined), on the GPU: paint ``strokes``
+        (an array of the mask's shape, nonzero = painted; ``how`` 'or' adds, 'andnot' erases, 'and'
+        keeps, 'xor' toggles) onto ``self.mask`` if given, then the per-slice disc morphology ``op``
+        ('erode' | 'dilate' | 'open' | 'close', ``radius`` 1..5 pixels) if given.  A voxel counts as set
+        when it is nonzero; the result is stored in ``self.mask`` as 0/1 in the mask's dtype,
+        ``mask_border`` and ``metadata['LungVolume']`` are recomputed from it, and the new mask is
+        returned.  ``N4HPvent``, ``defectArray`` and the VDP entries of ``metadata`` are left as they are
+        and belong to the old mask until calculate_VDP is run again."""
+        if op is None and strokes is None:
+            raise ValueError("edit_mask: give op, strokes or both")
+        how = _lib.paint_mode(how)
+        if op is not None:
+            op, radius = _lib._mask_edit_args(op, radius, 1)
+        old = np.asarray(self.mask)
+        with _lib.pooled_batch(*old.shape, 1, device=self.device) as B:
+            B.upload(None, (old != 0)[None])
+            if strokes is not None:
+                B.paint_mask(np.asarray(strokes)[None], how)
+            if op is not None:
+                B.edit_mask(op, radius)
+            new = B.download_mask()[0]
+        self.mask = new.astype(old.dtype)
+        self.mask_border = self.calculateBorder(self.mask)
+        self.metadata['LungVolume'] = np.sum(self.mask == 1) * np.prod(np.divide(self.vox, 10)) / 1000
+        return self.mask
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

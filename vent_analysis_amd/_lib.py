@@ -57,6 +57,44 @@ def dist_edges(bins, hi):
     return np.arange(int(bins) + 1) * (float(hi) / int(bins))
 
 
+VH_MASK_ERODE, VH_MASK_DILATE, VH_MASK_OPEN, VH_MASK_CLOSE = range(4)   # vh_batch_edit_mask ops
+VH_PAINT_OR, VH_PAINT_ANDNOT, VH_PAINT_AND, VH_PAINT_XOR = range(4)     # vh_batch_paint_mask modes
+_MASK_OPS = {"erode": VH_MASK_ERODE, "dilate": VH_MASK_DILATE, "open": VH_MASK_OPEN, "close": VH_MASK_CLOSE}
+_PAINT_MODES = {"or": VH_PAINT_OR, "andnot": VH_PAINT_ANDNOT, "and": VH_PAINT_AND, "xor": VH_PAINT_XOR}
+
+
+def _named_int(value, names, what):
+    """A name of ``names`` or one of its ints -> the int; anything else raises ValueError."""
+    if isinstance(value, str):
+        if value not in names:
+            raise ValueError(f"{what} is one of {sorted(names)}, got {value!r}")
+        return names[value]
+    if isinstance(value, (bool, float)) or not isinstance(value, (int, np.integer)) \
+            or int(value) not in names.values():
+        raise ValueError(f"{what} is one of {sorted(names)} or 0..{len(names) - 1}, got {value!r}")
+    return int(value)
+
+
+def paint_mode(how) -> int:
+    """'or' | 'andnot' | 'and' | 'xor' or the VH_PAINT_* ints -> the int; else ValueError."""
+    return _named_int(how, _PAINT_MODES, "paint mode")
+
+
+def _mask_edit_args(op, radius, n):
+    """(op int, radius int32 [n] contiguous) for vh_batch_edit_mask: ``op`` 'erode' | 'dilate' | 'open'
+    | 'close' or the VH_MASK_* ints, ``radius`` a scalar or one int per study, each 0..5.  ValueError
+    for what the library would refuse, so the message names the argument."""
+    op = _named_int(op, _MASK_OPS, "mask op")
+    r = np.asarray(radius)
+    if r.dtype == np.bool_ or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"edit_mask: radius is an int or one int per study, got {radius!r}")
+    if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != n):
+        raise ValueError(f"edit_mask: {n} studies, got radius of shape {r.shape}")
+    if r.size and (r.min() < 0 or r.max() > 5):
+        raise ValueError(f"edit_mask: every radius must be 0..5, got {radius!r}")
+    return op, np.ascontiguousarray(np.broadcast_to(r, (n,)), dtype=np.int32)
+
+
 def denoise_constants(sigma, strength=2.0, patch=1):
     """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
     sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
@@ -156,6 +194,10 @@ _SIGS = {
     "vh_batch_download_hp": ([_P, _P], ct.c_int),
     "vh_noise_sigma": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P], ct.c_int),
     "vh_denoise": ([_P, _P, _I64, _I64, _I64, _I64, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int, _P], ct.c_int),
+    "vh_batch_edit_mask": ([_P, ct.c_int, _P], ct.c_int),
+    "vh_batch_paint_mask": ([_P, _P, ct.c_int], ct.c_int),
+    "vh_batch_download_mask": ([_P, _P, _P], ct.c_int),
+    "vh_edit_mask": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -550,6 +592,26 @@ def denoise(hp, sigma, strength=2.0, search=3, patch=1, rician=False, device=0):
     return out
 
 
+def _mask_u8(a):
+    """Any dtype -> uint8 as it stands when it is uint8 already, else (a != 0) as 0 / 1."""
+    a = np.asarray(a)
+    return a if a.dtype == np.uint8 else (a != 0)
+
+
+def edit_mask(mask, op, radius=1, device=0):
+    """The per-slice disc morphology from host arrays (vh_edit_mask; the spec is in
+    include/vent_hip.h): ``mask`` a 3-D volume or a 4-D batch of any dtype, nonzero counting as set;
+    ``op`` 'erode' | 'dilate' | 'open' | 'close'; ``radius`` 0..5, a scalar or one int per study (a
+    study of radius 0 comes back as it went in).  Returns uint8 [B][R][C][Z]."""
+    c = context(device)
+    m = as_batch(_mask_u8(mask), np.uint8)
+    B, R, C, Z = m.shape
+    op, rad = _mask_edit_args(op, radius, B)
+    out = np.empty_like(m)
+    c.check(c.L.vh_edit_mask(c.h, _ptr(m), R, C, Z, B, op, _ptr(rad), _ptr(out), None), "vh_edit_mask")
+    return out
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -703,9 +765,10 @@ class Batch:
             pass
 
     def upload(self, hp, mask):
-        h = np.ascontiguousarray(hp, dtype=np.float32)
+        """``hp`` None uploads the masks alone (the resident HPvent stays as it is)."""
+        h = None if hp is None else np.ascontiguousarray(hp, dtype=np.float32)
         m = np.ascontiguousarray(mask, dtype=np.uint8)
-        if h.shape != self.shape or m.shape != self.shape:
+        if (h is not None and h.shape != self.shape) or m.shape != self.shape:
             raise ValueError(f"batch expects {self.shape}")
         self.ctx.check(self.L.vh_batch_upload(self.h, _ptr(h), _ptr(m)), "vh_batch_upload")
 
@@ -916,6 +979,37 @@ class Batch:
         out = np.empty(self.shape, np.float32)
         self.ctx.check(self.L.vh_batch_download_hp(self.h, _ptr(out)), "vh_batch_download_hp")
         return out
+
+    def edit_mask(self, op, radius=1):
+        """Enqueue the per-slice disc morphology of the resident masks (vh_batch_edit_mask; the spec
+        is in include/vent_hip.h): ``op`` 'erode' | 'dilate' | 'open' | 'close' (or VH_MASK_*),
+        ``radius`` 0..5, a scalar or one int per study -- a study of radius 0 keeps its mask byte for
+        byte, which is how one study is edited alone.  The next run() sees the edited masks.  After a
+        run, the calls that need a run raise ValueError until the next one.  Returns the radii used,
+        int32 [B]."""
+        op, rad = _mask_edit_args(op, radius, self.shape[0])
+        self.ctx.check(self.L.vh_batch_edit_mask(self.h, op, _ptr(rad)), "vh_batch_edit_mask")
+        return rad
+
+    def paint_mask(self, strokes, how="or"):
+        """Paint on the resident masks (vh_batch_paint_mask): with p = (strokes != 0), [B][R][C][Z] of
+        any dtype, the mask becomes s | p ('or'), s & ~p ('andnot'), s & p ('and') or s ^ p ('xor') as
+        0 / 1 bytes.  Like edit_mask it puts the batch back where upload() left it."""
+        how = paint_mode(how)
+        p = np.ascontiguousarray(_mask_u8(strokes), dtype=np.uint8)
+        if p.shape != self.shape:
+            raise ValueError(f"batch expects {self.shape}")
+        self.ctx.check(self.L.vh_batch_paint_mask(self.h, _ptr(p), how), "vh_batch_paint_mask")
+
+    def download_mask(self, count=False):
+        """The resident masks as they stand (vh_batch_download_mask), uint8 [B][R][C][Z]: after an
+        upload, an edit or a run.  With ``count`` also the voxels != 0 of each study, int64 [B],
+        counted on the device: (mask, count)."""
+        out = self.ctx.pinned.array(self.shape, np.uint8)   # page-locked: the D2H runs at the link rate
+
+        cnt = np.zeros(self.shape[0], np.int64) if count else None
+        self.ctx.check(self.L.vh_batch_download_mask(self.h, _ptr(out), _ptr(cnt)), "vh_batch_download_mask")
+        return (out, cnt) if count else out
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

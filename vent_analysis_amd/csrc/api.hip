@@ -1363,6 +1363,110 @@ int vh_denoise(vh_ctx *ctx, const float *hp, int64_t R, int64_t C, int64_t Z, in
     })
 }
 
+// ---- editing the masks of a device-resident batch (mask_edit.hip) -------------------------------
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_mask_edit(int op, const int32_t *radius, int64_t nb) {
+    if (op < VH_MASK_ERODE || op > VH_MASK_CLOSE)
+        throw VhError{VH_ERR_ARG, "op must be VH_MASK_ERODE, _DILATE, _OPEN or _CLOSE"};
+    if (!radius) throw VhError{VH_ERR_ARG, "null radius"};
+    for (int64_t i = 0; i < nb; ++i)
+        if (radius[i] < 0 || radius[i] > 5)
+            throw VhError{VH_ERR_ARG, "every radius must be 0..5 (study " + std::to_string(i) + ")"};
+}
+
+// Enqueue the morphology.  One step goes from d_mask into d_border (free until the next run writes
+// it) and the two buffers are exchanged, as batch_denoise exchanges its volumes; open and close go
+// there and back, so the intermediate is a mask volume of its own and the second step pads it like
+// any other.  d_hp, d_n4 and d_defect are not touched.
+static void batch_edit_mask(vh_batch *b, int op, const int32_t *radius) {
+    if (!vh_mask_edit_takes(b)) throw VhError{VH_ERR_ARG, "edit_mask: batch or tile count out of range"};
+    b->d_me_radius.reserve((size_t)b->nb);
+    // (pageable source: the copy has left radius when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_me_radius, radius, sizeof(int32_t) * (size_t)b->nb, hipMemcpyHostToDevice,
+                           b->stream));
+    const int first = (op == VH_MASK_ERODE || op == VH_MASK_OPEN) ? 1 : 0;
+    vh_mask_morph_launch(b, b->d_mask, b->d_border, b->d_me_radius, first);
+    if (op == VH_MASK_OPEN || op == VH_MASK_CLOSE)
+        vh_mask_morph_launch(b, b->d_border, b->d_mask, b->d_me_radius, 1 - first);
+    else
+        std::swap(b->d_mask, b->d_border);
+    batch_forget_run(b);
+}
+
+// The strokes go into d_lb (free until the next run writes it); the call waits until they have left
+// the caller's buffer -- an event behind the copy, not the stream -- and enqueues the kernel.
+static void batch_paint_mask(vh_batch *b, const uint8_t *strokes, int how) {
+    if (!vh_mask_edit_takes(b)) throw VhError{VH_ERR_ARG, "paint_mask: batch or tile count out of range"};
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipMemcpyAsync(b->d_lb, strokes, (size_t)b->nb * b->V, hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev, b->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(ev);
+    (void)hipEventDestroy(ev);
+    batch_forget_run(b);   // (d_lb is no longer the run's, whatever follows)
+    HIP_TRY(e);
+    vh_mask_paint_launch(b, b->d_mask, b->d_lb, how);
+}
+
+static void batch_download_mask(vh_batch *b, uint8_t *mask, int64_t *count) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (count) {
+        b->d_me_count.reserve(nb);
+        HIP_TRY(hipMemsetAsync(b->d_me_count, 0, sizeof(unsigned long long) * nb, st));
+        vh_mask_count_launch(b, b->d_mask, b->d_me_count);
+        HIP_TRY(hipMemcpyAsync(count, b->d_me_count, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, st));
+    }
+    if (mask) HIP_TRY(hipMemcpyAsync(mask, b->d_mask, nb * b->V, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_edit_mask(vh_batch *b, int op, const int32_t *radius) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        check_mask_edit(op, radius, b->nb);
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_edit_mask(b, op, radius);
+    })
+}
+
+int vh_batch_paint_mask(vh_batch *b, const uint8_t *strokes, int how) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        if (!strokes) throw VhError{VH_ERR_ARG, "null strokes"};
+        if (how < VH_PAINT_OR || how > VH_PAINT_XOR)
+            throw VhError{VH_ERR_ARG, "how must be VH_PAINT_OR, _ANDNOT, _AND or _XOR"};
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_paint_mask(b, strokes, how);
+    })
+}
+
+int vh_batch_download_mask(vh_batch *b, uint8_t *mask, int64_t *count) {
+    if (!b) return VH_ERR_ARG;
+    API_TRY(b->ctx, {
+        HIP_TRY(hipSetDevice(b->ctx->device));
+        batch_download_mask(b, mask, count);
+    })
+}
+
+int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch, int op,
+                 const int32_t *radius, uint8_t *out, int64_t *count) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_mask_edit(op, radius, batch);
+        HIP_TRY(hipSetDevice(ctx->device));
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, nullptr, mask);
+        batch_edit_mask(b, op, radius);
+        batch_download_mask(b, out, count);
+    })
+}
+
 // ---- TWIX recon (recon.hip) -------------------------------------------------------------------
 int vh_recon(vh_ctx *ctx, const double *k, int64_t n0, int64_t n1, int64_t nz, double *out) {
     API_TRY(ctx, {

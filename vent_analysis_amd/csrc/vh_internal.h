@@ -323,6 +323,10 @@ struct vh_batch {
     // vh_batch_denoise / vh_batch_noise_sigma (denoise.hip): on first demand
     Buf<float> d_dn_prm;             // [nb][2] the last denoise's inv_h2 and bias of each study
     Buf<float> d_dn_sigma;           // [nb] the last noise estimate
+    // vh_batch_edit_mask / vh_batch_download_mask (mask_edit.hip): on first demand.  The edits' scratch
+    // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
+    Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
+    Buf<unsigned long long> d_me_count;   // [nb] voxels != 0 of the resident mask (vh_batch_download_mask)
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -496,6 +500,14 @@ void vh_dist_launch(vh_batch *b, int norm, int n_bins, float hi, float scale);
 bool vh_denoise_takes(const vh_batch *b);
 void vh_denoise_launch(vh_batch *b, const float *src, float *dst, const float *d_prm, int S, int P, int rician);
 void vh_noise_sigma_launch(vh_batch *b, float *d_sigma);
+// mask_edit.hip: one disc dilation (erode 0) or erosion (erode 1) of every study, src -> dst (two
+// mask volumes of the batch), with d_radius [nb] in 0..5 (0: the study is copied);
+// vh_mask_edit_takes: the grid fits.  vh_mask_paint_launch: mask = paint(mask != 0, strokes != 0) in
+// place, both [nb][V].  vh_mask_count_launch: d_cnt [nb] (zeroed by the caller) += voxels != 0
+bool vh_mask_edit_takes(const vh_batch *b);
+void vh_mask_morph_launch(vh_batch *b, const uint8_t *src, uint8_t *dst, const int32_t *d_radius, int erode);
+void vh_mask_paint_launch(vh_batch *b, uint8_t *mask, const uint8_t *strokes, int how);
+void vh_mask_count_launch(vh_batch *b, const uint8_t *mask, unsigned long long *d_cnt);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
