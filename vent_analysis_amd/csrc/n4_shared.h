@@ -269,6 +269,78 @@ struct FitRing {
     int nr, i0;       // rows held, control row of row 0
 };
 
+#ifndef FIT_SUNROLL
+#define FIT_SUNROLL 4   // slice steps per stage-1 trip with one or two live slots, half with three or four (2 / 4 / 8 with one slot: 14.95 / 14.72 / 14.70 ms isolated, profiles/fitc_explore.jsonl)
+#endif
+#ifndef FIT_YG
+#define FIT_YG 4        // cols per stage-2 load group
+#endif
+
+// Stage 1 of fit_contract for the NQ live slots of a chunk: outputs o0 + lane + 64 q, q < NQ (NQ is
+// wave-uniform, the caller branches on it in scalar code, so a slot without outputs costs nothing).
+// The chains of a lane walk their slices in lockstep, SS steps per trip.  A trip is, in k_n4_study's
+// ISA (profiles/fitc_contract_isa.log): the 2 NQ SS ds_read_b64 of its steps back to back into registers of their own (no s_waitcnt
+// between them), then the fmas behind a counted lgkmcnt ladder, every chain adding its terms in
+// slice order.  A chain that is finished at a step reads its last element again and keeps its value.
+template <int NQ, bool INPLACE>
+__device__ __forceinline__ void fit_slices(const FitRing &rg, const Item &it, const TabV &T,
+                                           const double *Wk, int Z, int klo, int KT, int nyk, int nout,
+                                           int o0, double *S) {
+    constexpr int SS = NQ <= 2 ? FIT_SUNROLL : (FIT_SUNROLL + 1) / 2;
+    const int lane = threadIdx.x & 63;
+    double outv[NQ];
+    int qo[NQ], wo[NQ];     // the chain's first element in rg.q / Wk (indices, so that the reads keep
+                            // their bases' address spaces: ds_read from the ring, not flat loads)
+    int last[NQ], so[NQ];   // the chain's last step (-1: no term), the output's index in S (-1: none)
+    int maxlen = 0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        outv[q] = 0.0;
+        last[q] = -1;
+        so[q] = -1;
+        qo[q] = 0;
+        wo[q] = 0;
+        const int o = o0 + lane + 64 * q;
+        if (o >= nout) continue;
+        const int r = o / nyk, yk = o % nyk;
+        const int yy = yk / KT, k = klo + yk % KT, yv = it.y0 + yy;
+        const int zlo = yv == it.y0 ? it.z0 : 0, zhi = yv == it.y1 ? it.z1 : Z - 1;
+        const int2 kr = T.krz[k];
+        const int zs = max(zlo, kr.x), ze = min(zhi, kr.y);
+        qo[q] = r * rg.rowcap + (yv * Z - it.c0) + zs;
+        wo[q] = k * Z + zs;
+        last[q] = max(ze - zs, -1);
+        so[q] = r * rg.rowcap + yk;
+        maxlen = max(maxlen, last[q] + 1);
+    }
+#pragma unroll 1
+    for (int s = 0; s < maxlen; s += SS) {
+        double w[SS][NQ], v[SS][NQ];
+#pragma unroll
+        for (int j = 0; j < SS; ++j) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int ss = max(min(s + j, last[q]), 0);   // in-range read for finished chains
+                w[j][q] = Wk[wo[q] + ss];
+                v[j][q] = rg.q[qo[q] + ss];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // no fma moves up between the reads
+#pragma unroll
+        for (int j = 0; j < SS; ++j) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const double f = fma(w[j][q], v[j][q], outv[q]);
+                outv[q] = s + j <= last[q] ? f : outv[q];
+            }
+        }
+    }
+    if (INPLACE) wave_lds_order();   // in place: every read of the batch before any write
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+        if (so[q] >= 0) S[so[q]] = outv[q];
+}
+
 // INPLACE (n4_study): one chunk, S overwrites Q; otherwise (n4) chunks into the separate rg.sx.
 template <int P, bool INPLACE>
 __device__ void fit_contract(FitRing &rg, const Item &it, const TabV &T, const double *Wk, int ncy,
@@ -277,69 +349,57 @@ __device__ void fit_contract(FitRing &rg, const Item &it, const TabV &T, const d
     if (nr == 0) return;
     const int lane = threadIdx.x & 63;
     wave_lds_order();
-    const int klo = T.bz[it.y0 == it.y1 ? it.z0 : 0];
-    const int KT = T.bz[it.y0 == it.y1 ? it.z1 : Z - 1] + 4 - klo;
+    // the tile's control spans: wave-uniform table entries, as SGPRs (scalar loop bounds and branches)
+    const int klo = uni(T.bz[it.y0 == it.y1 ? it.z0 : 0]);
+    const int KT = uni(T.bz[it.y0 == it.y1 ? it.z1 : Z - 1]) + 4 - klo;
     const int nyk = it.ny * KT;
+    const int nout = nr * nyk;
     double *S = INPLACE ? rg.q : rg.sx;
-    for (int o0 = 0; o0 < nr * nyk; o0 += 64 * FIT_SO) {
-        // the FIT_SO outputs of a lane are independent fma chains over their slices: walk them in
-        // lockstep (step s of every chain together) so the LDS latency of one chain hides behind
-        // the others; each chain still adds its terms in slice order
-        double outv[FIT_SO];
-        const double *qp[FIT_SO], *wp[FIT_SO];
-        int len[FIT_SO];
-        int maxlen = 0;
-#pragma unroll
-        for (int q = 0; q < FIT_SO; ++q) {
-            outv[q] = 0.0;
-            len[q] = 0;
-            qp[q] = rg.q;
-            wp[q] = Wk;
-            const int o = o0 + lane + 64 * q;
-            if (o >= nr * nyk) continue;
-            const int r = o / nyk, yk = o % nyk;
-            const int yy = yk / KT, k = klo + yk % KT, yv = it.y0 + yy;
-            const int zlo = yv == it.y0 ? it.z0 : 0, zhi = yv == it.y1 ? it.z1 : Z - 1;
-            const int2 kr = T.krz[k];
-            const int zs = max(zlo, kr.x), ze = min(zhi, kr.y);
-            qp[q] = rg.q + r * rg.rowcap + (yv * Z - it.c0) + zs;
-            wp[q] = Wk + k * Z + zs;
-            len[q] = max(ze - zs + 1, 0);
-            maxlen = max(maxlen, len[q]);
-        }
-#ifndef FIT_SUNROLL
-#define FIT_SUNROLL 4   // slice steps per trip: the next steps' LDS reads issued together (r4ay: 18.44 -> 18.39 ms)
-#endif
-#pragma unroll FIT_SUNROLL
-        for (int s = 0; s < maxlen; ++s) {
-#pragma unroll
-            for (int q = 0; q < FIT_SO; ++q) {
-                const int ss = min(s, max(len[q] - 1, 0));   // in-range read for finished chains
-                const double v = fma(wp[q][ss], qp[q][ss], outv[q]);
-                outv[q] = s < len[q] ? v : outv[q];
-            }
-        }
-        if (INPLACE) wave_lds_order();   // in place: every read of the batch before any write
-#pragma unroll
-        for (int q = 0; q < FIT_SO; ++q) {
-            const int o = o0 + lane + 64 * q;
-            if (o < nr * nyk) S[(o / nyk) * rg.rowcap + o % nyk] = outv[q];
-        }
+    for (int o0 = 0; o0 < nout; o0 += 64 * FIT_SO) {
+        // live slots of this chunk (1 .. FIT_SO): only they run, by a scalar branch
+        const int nq = uni(min(FIT_SO, (nout - o0 + 63) >> 6));
+        if (nq == 1) fit_slices<1, INPLACE>(rg, it, T, Wk, Z, klo, KT, nyk, nout, o0, S);
+        else if (nq == 2) fit_slices<2, INPLACE>(rg, it, T, Wk, Z, klo, KT, nyk, nout, o0, S);
+        else if (nq == 3) fit_slices<3, INPLACE>(rg, it, T, Wk, Z, klo, KT, nyk, nout, o0, S);
+        else fit_slices<4, INPLACE>(rg, it, T, Wk, Z, klo, KT, nyk, nout, o0, S);
         if (INPLACE) break;   // nbmax keeps a batch within one chunk
     }
+    static_assert(FIT_SO == 4, "fit_contract branches over 1 .. 4 live slots");
     wave_lds_order();
-    const int jlo = T.by[it.y0];
-    const int JT = T.by[it.y1] + 4 - jlo;
+    const int jlo = uni(T.by[it.y0]);
+    const int JT = uni(T.by[it.y1]) + 4 - jlo;
     const int njk = JT * KT;
     for (int o = lane; o < nr * njk; o += 64) {
         const int r = o / njk, jk = o % njk;
         const int j = jlo + jk / KT, kk = jk % KT, k = klo + kk;
-        const double *sr = S + r * rg.rowcap;
+        const double *sr = S + r * rg.rowcap + kk;
         double acc = 0.0;
-        for (int yy = 0; yy < it.ny; ++yy) {
-            const int d = j - T.by[it.y0 + yy];
-            if (d < 0 || d > 3) continue;
-            acc = fma(wpow<P>(wsel(T.wy[it.y0 + yy], d)), sr[yy * KT + kk], acc);
+        // FIT_YG cols per trip, two load groups with one wait each: the cols' by entries, then the one
+        // wy component each col's term takes (d clamped for a col outside the output's window) with
+        // its S value; then the terms are added in ascending col order, and a col outside the window
+        // (or past the tile) leaves acc as it is
+#pragma unroll 1
+        for (int yg = 0; yg < it.ny; yg += FIT_YG) {
+            int d[FIT_YG];
+            float wv[FIT_YG];
+            double sv[FIT_YG];
+#pragma unroll
+            for (int g = 0; g < FIT_YG; ++g) d[g] = T.by[it.y0 + min(yg + g, it.ny - 1)];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < FIT_YG; ++g) {
+                const int yc = min(yg + g, it.ny - 1);
+                d[g] = j - d[g];
+                wv[g] = reinterpret_cast<const float *>(T.wy + it.y0 + yc)[min(max(d[g], 0), 3)];
+                sv[g] = sr[yc * KT];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < FIT_YG; ++g) {
+                double f = fma(wpow<P>(wv[g]), sv[g], acc);
+                __asm__ volatile("" : "+v"(f));   // keeps the select a select (not a branch per col)
+                acc = (yg + g < it.ny && d[g] >= 0 && d[g] <= 3) ? f : acc;
+            }
         }
         if (acc != 0.0) {
             const int64_t e = ((int64_t)(rg.i0 + r) * ncy + j) * ncz + k;
@@ -366,7 +426,7 @@ __device__ __forceinline__ void fit_ring_begin(FitRing &rg, const Item &it, cons
                                                int nb_ring) {
     const int klo = T.bz[it.y0 == it.y1 ? it.z0 : 0];
     const int KT = T.bz[it.y0 == it.y1 ? it.z1 : Z - 1] + 4 - klo;
-    rg.nbmax = INPLACE ? max(1, min(nb_ring, 64 * FIT_SO / (it.ny * KT))) : nb_ring;
+    rg.nbmax = INPLACE ? uni(max(1, min(nb_ring, 64 * FIT_SO / (it.ny * KT)))) : nb_ring;
     rg.nr = 0;
 }
 
