@@ -96,6 +96,19 @@ static void resolve_timers(vh_batch *b) {
     if (!ks.empty()) kst_reset(b);
 }
 
+// the resolved totals of one kernel class of b (a null b, or a class that never ran: zeros)
+static void timer_totals(vh_batch *b, const char *name, double *total_ms, int64_t *launches, double *bytes) {
+    KTimer t;
+    if (b) {
+        resolve_timers(b);
+        auto it = b->timers.find(name);
+        if (it != b->timers.end()) t = it->second;
+    }
+    *total_ms = t.total_ms;
+    *launches = t.launches;
+    if (bytes) *bytes = t.bytes_per_launch;
+}
+
 // ---------------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------------
@@ -120,6 +133,15 @@ static int fail(vh_ctx *c, int code, const std::string &msg) {
         return fail(ctx, VH_ERR_HIP, "unknown error");                                       \
     }                                                                                        \
     return VH_OK;
+
+// Every vh_batch_* entry point but vh_batch_destroy: a null handle is VH_ERR_ARG; otherwise API_TRY on
+// the batch's context, with its device current.
+#define BATCH_TRY(b, ...)                                                                    \
+    if (!(b)) return VH_ERR_ARG;                                                             \
+    API_TRY((b)->ctx, {                                                                      \
+        HIP_TRY(hipSetDevice((b)->ctx->device));                                             \
+        __VA_ARGS__                                                                          \
+    })
 
 // Buf's allocator (devbuf.h): the library's only device and pinned-host allocations, but for
 // vh_host_alloc / vh_host_free, whose memory the caller owns
@@ -273,23 +295,11 @@ static void batch_run(vh_batch *b, const vh_run_opts &o, int n4_src) {
     b->n4_mode = o.n4_mode;
     if (o.do_n4) check_n4_params(b, o.n4);
     vh_launch_mask_stats(b);
-    const float *n4 = b->d_hp;
-    if (o.do_n4) {
-        vh_launch_n4(b, o.n4);
-        n4 = b->d_n4;
-    } else if (n4_src == 2) {
-        n4 = b->d_n4;
-    }
-    vh_launch_vdp_chain(b, n4, o);
-    b->have_result = true;
-    b->d_n4_last = n4;
-    b->km_valid = false;
-    b->sel_valid = false;
-    b->ci_fresh = false;          // the run replaced the defect maps, and the mask statistics
-    b->mt_layout_valid = false;
-    b->ov_valid = false;
-    b->mt_valid = false;
-    b->dist_valid = false;
+    if (o.do_n4) vh_launch_n4(b, o.n4);
+    const bool from_n4 = o.do_n4 || n4_src == 2;
+    vh_launch_vdp_chain(b, from_n4 ? b->d_n4.get() : b->d_hp.get(), o);
+    // (the run replaced the defect maps and the mask statistics: whatever was derived from them is gone)
+    b->state.ran(from_n4 ? N4Source::n4 : N4Source::hp, o.do_kmeans != 0);
 }
 
 // the study kernel's spin-wait watchdog (n4_study.hip st_spin) leaves N4State.active = -2
@@ -306,17 +316,24 @@ static void d2h_on_stream(vh_batch *b, void *dst, const void *src, size_t bytes)
     HIP_TRY(hipStreamSynchronize(b->stream));
 }
 
-static void fill_results_from(const vh_batch *b, const VolScalars *sc, const N4State *st, vh_vdp_result *res);
-
-static void fill_results(vh_batch *b, vh_vdp_result *res) {
+// host copies of every study's scalars / N4 state; each waits for the batch's stream
+static std::vector<VolScalars> read_scalars(vh_batch *b) {
     std::vector<VolScalars> sc(b->nb);
     d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);
-    std::vector<N4State> st;
-    if (b->opts.do_n4) {
-        st.resize(b->nb);
-        d2h_on_stream(b, st.data(), b->d_st, sizeof(N4State) * b->nb);
+    return sc;
+}
+static std::vector<N4State> read_n4_states(vh_batch *b) {
+    std::vector<N4State> st(b->nb);
+    d2h_on_stream(b, st.data(), b->d_st, sizeof(N4State) * b->nb);
+    return st;
+}
+
+// the host-buffer calls' last check, after their outputs are written; with_snr: calculate_SNR's too
+static void throw_if_empty_mask(const std::vector<VolScalars> &sc, bool with_snr = false) {
+    for (const VolScalars &s : sc) {
+        if (s.n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
+        if (with_snr && !s.snr_ok) throw VhError{VH_ERR_ARG, "calculate_SNR: no masked column > 0"};
     }
-    fill_results_from(b, sc.data(), st.data(), res);
 }
 
 // per-study results from host copies of the scalars (and N4 states when the batch ran N4)
@@ -351,8 +368,9 @@ static void fill_results_from(const vh_batch *b, const VolScalars *sc, const N4S
     }
 }
 
-static void batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *border, uint8_t *lb,
-                           vh_vdp_result *res) {
+// returns the scalars it read for res (none when res is null)
+static std::vector<VolScalars> batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *border,
+                                              uint8_t *lb, vh_vdp_result *res) {
     hipStream_t st = b->stream;
     HIP_TRY(hipStreamSynchronize(st));
     const size_t NV = (size_t)b->nb * b->V;
@@ -360,7 +378,11 @@ static void batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *bor
     if (defect) HIP_TRY(hipMemcpy(defect, b->d_defect, NV, hipMemcpyDeviceToHost));
     if (border) HIP_TRY(hipMemcpy(border, b->d_border, NV, hipMemcpyDeviceToHost));
     if (lb) HIP_TRY(hipMemcpy(lb, b->d_lb, NV, hipMemcpyDeviceToHost));
-    if (res) fill_results(b, res);
+    if (!res) return {};
+    const std::vector<VolScalars> sc = read_scalars(b);
+    const std::vector<N4State> n4st = b->opts.do_n4 ? read_n4_states(b) : std::vector<N4State>();
+    fill_results_from(b, sc.data(), n4st.data(), res);
+    return sc;
 }
 
 static void pipe_free(vh_pipe *p) {
@@ -377,8 +399,10 @@ static void pipe_free(vh_pipe *p) {
     delete p;   // the slots' staging buffers
 }
 
-// The context's cached scratch batch for the host-buffer entry points (caller holds ctx->mu).
+// The context's cached scratch batch for the host-buffer entry points (caller holds ctx->mu), with
+// the context's device current for what the caller enqueues on it.
 static vh_batch *scratch_batch(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t nb) {
+    HIP_TRY(hipSetDevice(ctx->device));
     vh_batch *&s = ctx->scratch;
     if (s && s->R == R && s->C == C && s->Z == Z && s->nb == nb) return s;
     if (s) {
@@ -388,6 +412,29 @@ static vh_batch *scratch_batch(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int
     s = nullptr;
     s = batch_new(ctx, R, C, Z, nb);
     return s;
+}
+
+// the default options with N4 off: the host-buffer calls that bring their own N4 volume
+static vh_run_opts chain_only_opts(float thresh, bool do_snr, bool do_kmeans, int profile) {
+    vh_run_opts o;
+    vh_default_run_opts(&o);
+    o.do_n4 = 0;
+    o.do_snr = do_snr;
+    o.do_kmeans = do_kmeans;
+    o.thresh = thresh;
+    o.profile = profile;
+    return o;
+}
+
+// Host arrays in, the chain run on the scratch batch (caller holds ctx->mu): n4 goes to d_n4, which the
+// chain reads; hp is nullable.  The caller enqueues its feature and downloads.
+static vh_batch *run_host_arrays(vh_ctx *ctx, const float *hp, const float *n4, const uint8_t *mask, int64_t R,
+                                 int64_t C, int64_t Z, int64_t batch, const vh_run_opts &o) {
+    vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+    HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * (size_t)batch * b->V, hipMemcpyHostToDevice, b->stream));
+    batch_upload(b, hp, mask);
+    batch_run(b, o, 2);
+    return b;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -508,18 +555,15 @@ int vh_n4(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R, int64_t 
         vh_launch_n4(b, o.n4);
         HIP_TRY(hipStreamSynchronize(b->stream));
         HIP_TRY(hipMemcpy(out, b->d_n4, sizeof(float) * batch * b->V, hipMemcpyDeviceToHost));
-        std::vector<N4State> st(batch);
-        HIP_TRY(hipMemcpy(st.data(), b->d_st, sizeof(N4State) * batch, hipMemcpyDeviceToHost));
+        const std::vector<N4State> st = read_n4_states(b);
         check_n4_watchdog(st.data(), batch);
         for (int64_t i = 0; i < batch; ++i)
             for (int l = 0; l < prm->n_levels; ++l) {
                 if (iters) iters[i * prm->n_levels + l] = st[i].iters_level[l];
                 if (conv) conv[i * prm->n_levels + l] = st[i].conv_level[l];
             }
-        std::vector<VolScalars> sc(batch);
-        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < batch; ++i)
-            if (sc[i].n_mask1 < 2) throw VhError{VH_ERR_EMPTY, "N4 needs at least 2 voxels with mask == 1"};
+        for (const VolScalars &s : read_scalars(b))
+            if (s.n_mask1 < 2) throw VhError{VH_ERR_EMPTY, "N4 needs at least 2 voxels with mask == 1"};
     })
 }
 
@@ -529,7 +573,6 @@ int vh_border(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, in
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!a || !border) throw VhError{VH_ERR_ARG, "null buffer"};
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
-        HIP_TRY(hipSetDevice(ctx->device));
         b->profile = false;
         const size_t NV = (size_t)batch * b->V;
         HIP_TRY(hipMemcpyAsync(b->d_defect, a, NV, hipMemcpyHostToDevice, b->stream));
@@ -546,13 +589,10 @@ int vh_snr(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R, int64_t
         if (!hp || !mask || !snr) throw VhError{VH_ERR_ARG, "null buffer"};
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
         batch_upload(b, hp, mask);
-        HIP_TRY(hipSetDevice(ctx->device));
         b->profile = false;
         vh_launch_mask_stats(b);
         vh_launch_snr(b);
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        std::vector<VolScalars> sc(batch);
-        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
+        const std::vector<VolScalars> sc = read_scalars(b);
         for (int64_t i = 0; i < batch; ++i) {
             if (!sc[i].snr_ok) throw VhError{VH_ERR_ARG, "calculate_SNR: no masked column > 0 (numpy min of an empty array)"};
             snr[i] = sc[i].snr;
@@ -566,24 +606,10 @@ int vh_vdp(vh_ctx *ctx, const float *hp, const float *n4, const uint8_t *mask, i
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!n4 || !mask || !res || !vox) throw VhError{VH_ERR_ARG, "null buffer"};
-        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
-        const size_t NV = (size_t)batch * b->V;
-        HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
-        batch_upload(b, hp, mask);
-        vh_run_opts o;
-        vh_default_run_opts(&o);
-        o.do_n4 = 0;
-        o.do_snr = hp != nullptr;
-        o.thresh = thresh;
+        vh_run_opts o = chain_only_opts(thresh, hp != nullptr, true, 0);
         for (int i = 0; i < 3; ++i) o.vox[i] = vox[i];
-        batch_run(b, o, 2);
-        batch_download(b, nullptr, defect, defect_border, lb, res);
-        std::vector<VolScalars> sc(batch);
-        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < batch; ++i) {
-            if (sc[i].n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
-            if (hp && !sc[i].snr_ok) throw VhError{VH_ERR_ARG, "calculate_SNR: no masked column > 0"};
-        }
+        vh_batch *b = run_host_arrays(ctx, hp, n4, mask, R, C, Z, batch, o);
+        throw_if_empty_mask(batch_download(b, nullptr, defect, defect_border, lb, res), hp != nullptr);
     })
 }
 
@@ -608,7 +634,6 @@ static void ci_host(vh_ctx *ctx, const uint8_t *defect, int64_t R, int64_t C, in
     if (!defect || !t) throw VhError{VH_ERR_ARG, "null defect map / table"};
     if (t->ctx != ctx) throw VhError{VH_ERR_ARG, "sphere table of another context"};
     vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
-    HIP_TRY(hipSetDevice(ctx->device));
     b->profile = ctx->profile != 0;
     const size_t NV = (size_t)batch * b->V;
     HIP_TRY(hipMemcpyAsync(b->d_defect, defect, NV, hipMemcpyHostToDevice, b->stream));
@@ -708,27 +733,24 @@ int vh_batch_destroy(vh_batch *b) {
 }
 
 int vh_batch_upload(vh_batch *b, const float *hp, const uint8_t *mask) {
-    API_TRY(b->ctx, {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        batch_upload(b, hp, mask);
-    })
+    BATCH_TRY(b, { batch_upload(b, hp, mask); })
 }
 
 int vh_batch_run(vh_batch *b, const vh_run_opts *opts) {
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!opts) throw VhError{VH_ERR_ARG, "null options"};
         batch_run(b, *opts, opts->do_n4 ? 0 : 1);
     })
 }
 
 int vh_batch_sync(vh_batch *b) {
-    API_TRY(b->ctx, { HIP_TRY(hipStreamSynchronize(b->stream)); })
+    BATCH_TRY(b, { HIP_TRY(hipStreamSynchronize(b->stream)); })
 }
 
 int vh_batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *defect_border, uint8_t *lb,
                       vh_vdp_result *res) {
-    API_TRY(b->ctx, {
-        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    BATCH_TRY(b, {
+        b->state.need_run();
         batch_download(b, n4, defect, defect_border, lb, res);
     })
 }
@@ -736,12 +758,10 @@ int vh_batch_download(vh_batch *b, float *n4, uint8_t *defect, uint8_t *defect_b
 // The CI of the resident defect maps (the last run's, or vh_batch_set_defect's): enqueue only.  The
 // table's radii are copied into the batch, so vh_batch_download_ci needs the table no more.
 int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox) {
-    if (!b || !t) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    if (!t) return VH_ERR_ARG;
+    BATCH_TRY(b, {
         if (t->ctx != b->ctx) throw VhError{VH_ERR_ARG, "sphere table of another context"};
-        if (!b->have_result && !b->have_defect)
-            throw VhError{VH_ERR_ARG, "no defect maps resident: vh_batch_run or vh_batch_set_defect first"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+        b->state.need_defect();
         std::lock_guard<std::mutex> lock(b->ctx->mu);   // against vh_ci_table_destroy of another thread
         hipEvent_t &ev = t->users[b];
         if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -755,93 +775,78 @@ int vh_batch_ci(vh_batch *b, const vh_ci_table *t, double minvox) {
             throw;
         }
         HIP_TRY(hipEventRecord(ev, b->stream));
-        b->ci_nbs = t->nbs;
-        b->ci_minvox = minvox;
-        b->have_ci = true;
-        b->ci_fresh = true;
+        b->state.ci_enqueued(t->nbs, minvox);
     })
 }
 
 int vh_batch_set_defect(vh_batch *b, const uint8_t *defect) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!defect) throw VhError{VH_ERR_ARG, "null defect maps"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
         HIP_TRY(hipMemcpyAsync(b->d_defect, defect, (size_t)b->nb * b->V, hipMemcpyHostToDevice, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
-        b->have_defect = true;
-        b->sel_valid = false;
-        b->ci_fresh = false;
+        b->state.defect_replaced();
     })
 }
 
 // the argument checks of the selection calls (host only: nothing is enqueued before they pass)
-static void check_select(const vh_batch *b, int source, int medfilt) {
+static void check_select_args(int source, int medfilt) {
     if (source < VH_DEFECT_MEAN || source > VH_DEFECT_KM)
         throw VhError{VH_ERR_ARG, "source must be VH_DEFECT_MEAN, _LB or _KM"};
     if (medfilt < 0 || medfilt > 2) throw VhError{VH_ERR_ARG, "medfilt must be 0, 1 or 2"};
-    if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
-    if (source == VH_DEFECT_KM && !b->opts.do_kmeans)
-        throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
+}
+static void check_select(const vh_batch *b, int source, int medfilt) {
+    check_select_args(source, medfilt);
+    b->state.need_run();
+    if (source == VH_DEFECT_KM) b->state.need_kmeans();
 }
 
 static void batch_select(vh_batch *b, int source, int medfilt) {
     // the label map rides along once a caller has asked for it (d_km exists) and the run has cuts
     uint8_t *km = b->opts.do_kmeans ? b->d_km : nullptr;
-    if (!vh_launch_defect_select(b, b->d_n4_last, b->opts.thresh, source, medfilt, km))
+    if (!vh_launch_defect_select(b, b->n4_last(), b->opts.thresh, source, medfilt, km))
         throw VhError{VH_ERR_ARG, "vh_batch_select_defect: this shape has no plane-sweep geometry"};
-    if (km) b->km_valid = true;
-    b->sel_valid = true;
-    b->ci_fresh = false;
+    b->state.selected(km != nullptr);
 }
 
-static void batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count) {
+// returns the scalars it read for count
+static std::vector<VolScalars> batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km,
+                                                     int64_t *count) {
     const size_t NV = (size_t)b->nb * b->V;
     hipStream_t st = b->stream;
-    if (km && !b->km_valid) {
+    if (km && !b->state.labels_valid()) {
         b->d_km.reserve(NV);
-        vh_launch_km_labels(b, b->d_n4_last, b->d_km);
-        b->km_valid = true;
+        vh_launch_km_labels(b, b->n4_last(), b->d_km);
+        b->state.labels_built();
     }
     if (defect) HIP_TRY(hipMemcpyAsync(defect, b->d_defect, NV, hipMemcpyDeviceToHost, st));
     if (border) HIP_TRY(hipMemcpyAsync(border, b->d_border, NV, hipMemcpyDeviceToHost, st));
     if (km) HIP_TRY(hipMemcpyAsync(km, b->d_km, NV, hipMemcpyDeviceToHost, st));
-    std::vector<VolScalars> sc(b->nb);
-    d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);   // synchronises the stream
+    std::vector<VolScalars> sc = read_scalars(b);   // synchronises the stream
     if (count)
-        for (int64_t i = 0; i < b->nb; ++i) count[i] = b->sel_valid ? sc[i].n_sel : sc[i].n_defect;
+        for (int64_t i = 0; i < b->nb; ++i) count[i] = b->state.selection_on() ? sc[i].n_sel : sc[i].n_defect;
+    return sc;
 }
 
 int vh_batch_select_defect(vh_batch *b, int source, int medfilt) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         check_select(b, source, medfilt);
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_select(b, source, medfilt);
     })
 }
 
 int vh_batch_download_defect(vh_batch *b, uint8_t *defect, uint8_t *border, uint8_t *km, int64_t *count) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
-        if (km && !b->opts.do_kmeans)
-            throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+    BATCH_TRY(b, {
+        b->state.need_run();
+        if (km) b->state.need_kmeans();
         batch_download_defect(b, defect, border, km, count);
     })
 }
 
 int vh_batch_km_cuts(vh_batch *b, float *cuts) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!cuts) throw VhError{VH_ERR_ARG, "null cuts"};
-        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
-        if (!b->opts.do_kmeans)
-            throw VhError{VH_ERR_ARG, "the last vh_batch_run had do_kmeans = 0: no k-means partition"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        std::vector<VolScalars> sc(b->nb);
-        d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);
+        b->state.need_kmeans();
+        const std::vector<VolScalars> sc = read_scalars(b);
         for (int64_t i = 0; i < b->nb; ++i)
             for (int j = 0; j < 3; ++j) {
                 // (an empty study has no cuts: km_valid is 0 from the run's initialisation)
@@ -861,34 +866,17 @@ int vh_defect_map(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, 
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!n4 || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
-        if (source < VH_DEFECT_MEAN || source > VH_DEFECT_KM || medfilt < 0 || medfilt > 2)
-            throw VhError{VH_ERR_ARG, "source must be VH_DEFECT_MEAN, _LB or _KM and medfilt 0, 1 or 2"};
-        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
-        const size_t NV = (size_t)batch * b->V;
-        HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
-        batch_upload(b, nullptr, mask);
-        vh_run_opts o;
-        vh_default_run_opts(&o);
-        o.do_n4 = 0;
-        o.do_snr = 0;
-        o.do_kmeans = source == VH_DEFECT_KM || km != nullptr;
-        o.thresh = thresh;
-        o.profile = ctx->profile;
-        batch_run(b, o, 2);
+        check_select_args(source, medfilt);
+        const vh_run_opts o = chain_only_opts(thresh, false, source == VH_DEFECT_KM || km != nullptr, ctx->profile);
+        vh_batch *b = run_host_arrays(ctx, nullptr, n4, mask, R, C, Z, batch, o);
         batch_select(b, source, medfilt);
-        batch_download_defect(b, defect, border, km, count);
-        std::vector<VolScalars> sc(batch);
-        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < batch; ++i)
-            if (sc[i].n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
+        throw_if_empty_mask(batch_download_defect(b, defect, border, km, count));
     })
 }
 
 int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *ci_scalar, int32_t *status) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->have_ci) throw VhError{VH_ERR_ARG, "vh_batch_ci has not been called"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+    BATCH_TRY(b, {
+        b->state.need_ci();
         const size_t NV = (size_t)b->nb * b->V;
         if (ci_array) {
             b->d_ci_map.reserve(NV);
@@ -897,8 +885,7 @@ int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *
         }
         if (shell)
             HIP_TRY(hipMemcpyAsync(shell, b->d_ci_shell16, sizeof(int16_t) * NV, hipMemcpyDeviceToHost, b->stream));
-        std::vector<VolScalars> sc(b->nb);
-        d2h_on_stream(b, sc.data(), b->d_sc, sizeof(VolScalars) * b->nb);   // synchronises the stream
+        const std::vector<VolScalars> sc = read_scalars(b);   // synchronises the stream
         vh_ci_debug_check();
         for (int64_t i = 0; i < b->nb; ++i) {
             if (ci_scalar) ci_scalar[i] = sc[i].ci_scalar;
@@ -908,7 +895,7 @@ int vh_batch_download_ci(vh_batch *b, double *ci_array, int16_t *shell, double *
 }
 
 int vh_batch_cohort_hist(vh_batch *b, uint64_t *hist) {
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         HIP_TRY(hipStreamSynchronize(b->stream));
         HIP_TRY(hipMemcpy(hist, b->d_cohort, sizeof(uint64_t) * VH_COHORT_BINS, hipMemcpyDeviceToHost));
     })
@@ -920,7 +907,7 @@ const char *vh_batch_kernel_names(void) {
 }
 
 int vh_batch_reset_timers(vh_batch *b) {
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         HIP_TRY(hipStreamSynchronize(b->stream));
         clear_timers(b);
     })
@@ -928,18 +915,7 @@ int vh_batch_reset_timers(vh_batch *b) {
 
 int vh_batch_kernel_time(vh_batch *b, const char *name, double *total_ms, int64_t *launches,
                          double *bytes_per_launch) {
-    API_TRY(b->ctx, {
-        resolve_timers(b);
-        auto it = b->timers.find(name);
-        if (it == b->timers.end()) {
-            *total_ms = 0; *launches = 0;
-            if (bytes_per_launch) *bytes_per_launch = 0;
-        } else {
-            *total_ms = it->second.total_ms;
-            *launches = it->second.launches;
-            if (bytes_per_launch) *bytes_per_launch = it->second.bytes_per_launch;
-        }
-    })
+    BATCH_TRY(b, { timer_totals(b, name, total_ms, launches, bytes_per_launch); })
 }
 
 int vh_ctx_profile(vh_ctx *ctx, int on) {
@@ -957,27 +933,17 @@ int vh_ctx_kernel_time(vh_ctx *ctx, const char *name, double *total_ms, int64_t 
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!name || !total_ms || !launches) throw VhError{VH_ERR_ARG, "null argument"};
-        *total_ms = 0;
-        *launches = 0;
-        if (ctx->scratch) {
-            resolve_timers(ctx->scratch);
-            auto it = ctx->scratch->timers.find(name);
-            if (it != ctx->scratch->timers.end()) {
-                *total_ms = it->second.total_ms;
-                *launches = it->second.launches;
-            }
-        }
+        timer_totals(ctx->scratch, name, total_ms, launches, nullptr);
     })
 }
 
 int vh_batch_study_times(vh_batch *b, double *us) {
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!us) throw VhError{VH_ERR_ARG, "null buffer"};
         HIP_TRY(hipStreamSynchronize(b->stream));
         for (int64_t i = 0; i < b->nb; ++i) us[i] = 0.0;
-        if (!b->have_result || !b->opts.do_n4 || !b->n4_used_study) return VH_OK;
-        std::vector<N4State> st(b->nb);
-        d2h_on_stream(b, st.data(), b->d_st, sizeof(N4State) * b->nb);
+        if (!b->state.has_run() || !b->opts.do_n4 || !b->n4_used_study) return VH_OK;
+        const std::vector<N4State> st = read_n4_states(b);
         int rate_khz = 0;
         HIP_TRY(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, b->ctx->device));
         if (rate_khz <= 0) throw VhError{VH_ERR_HIP, "no device wall clock rate"};
@@ -1003,7 +969,6 @@ int vh_overlay(vh_ctx *ctx, const float *n4, const uint8_t *defect, int64_t R, i
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!n4 || !defect || !rgb) throw VhError{VH_ERR_ARG, "overlay: null buffer"};
-        HIP_TRY(hipSetDevice(ctx->device));
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
         const size_t NV = (size_t)batch * R * C * Z;
         HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
@@ -1026,7 +991,6 @@ int vh_montage(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, const void *proton,
         if (!proton || !hp || !n4 || !mask_border || !defect || !parula || !crop || !image)
             throw VhError{VH_ERR_ARG, "montage: null buffer"};
         check_dims(R, C, Z, 1);
-        HIP_TRY(hipSetDevice(ctx->device));
         vh_batch *b = scratch_batch(ctx, R, C, Z, 1);
         vh_montage_run(b->stream, R, C, Z, proton, proton_is64, hp, hp_is64, n4, mask_border, defect,
                        ci, parula, prow, crop, image);
@@ -1039,27 +1003,23 @@ int vh_montage(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, const void *proton,
 // their own, allocated on first demand like d_km: a rendering writes nothing
 // another call on the batch reads.
 int vh_batch_overlay(vh_batch *b) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    BATCH_TRY(b, {
+        b->state.need_run();
         if (b->nb > 65535 || b->R > 65535) throw VhError{VH_ERR_ARG, "overlay: batch or rows out of range"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
         const size_t NV = (size_t)b->nb * b->V;
         b->d_ov_rgb.reserve(3 * NV);
         b->d_ov_mm.reserve(2 * (size_t)b->nb);
         // N4 twice (min/max, then the frames), the defect map, 3 bytes out
         ScopedKTimer tm(b, "overlay_b", 12.0 * (double)NV);
-        vh_overlay_launch(b->stream, b->d_n4_last, b->d_defect, b->R, b->C, b->Z, b->nb, b->d_ov_mm, b->d_ov_rgb);
-        b->ov_valid = true;
+        vh_overlay_launch(b->stream, b->n4_last(), b->d_defect, b->R, b->C, b->Z, b->nb, b->d_ov_mm, b->d_ov_rgb);
+        b->state.overlay_enqueued();
     })
 }
 
 int vh_batch_download_overlay(vh_batch *b, uint8_t *rgb) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!rgb) throw VhError{VH_ERR_ARG, "null buffer"};
-        if (!b->ov_valid) throw VhError{VH_ERR_ARG, "vh_batch_overlay has not been called since the last run"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+        b->state.need_overlay();
         d2h_on_stream(b, rgb, b->d_ov_rgb, 3 * (size_t)b->nb * b->V);
     })
 }
@@ -1067,9 +1027,8 @@ int vh_batch_download_overlay(vh_batch *b, uint8_t *rgb) {
 // cropToData of every resident mask and the compact buffer's layout; cached until the next run.
 // One small kernel, a copy of nb x 32 bytes back, the prefix on the host, nb + 1 records up.
 static void batch_montage_layout(vh_batch *b) {
-    if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
-    if (b->mt_layout_valid) return;
-    HIP_TRY(hipSetDevice(b->ctx->device));
+    b->state.need_run();
+    if (b->state.layout_is_cached()) return;
     const int64_t nb = b->nb;
     b->d_mt_crop.reserve((size_t)nb * 8);
     b->d_mt_st.reserve((size_t)nb + 1);
@@ -1097,12 +1056,11 @@ static void batch_montage_layout(vh_batch *b) {
     b->mt_st[nb].wg0 = wg;
     HIP_TRY(hipMemcpyAsync(b->d_mt_st, b->mt_st.data(), sizeof(MtStudy) * (nb + 1), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    b->mt_layout_valid = true;
+    b->state.layout_cached();
 }
 
 int vh_batch_montage_layout(vh_batch *b, int64_t *crop, int64_t *offset, int32_t *status) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         batch_montage_layout(b);
         for (int64_t i = 0; i < b->nb; ++i) {
             const MtStudy &s = b->mt_st[i];
@@ -1120,12 +1078,10 @@ int vh_batch_montage_layout(vh_batch *b, int64_t *crop, int64_t *offset, int32_t
 // which waits for the stream once).  The CI panel is drawn when vh_batch_ci was enqueued after the
 // last change of the resident defect maps.
 int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int64_t prow) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    BATCH_TRY(b, {
+        b->state.need_run();
         if (!parula || prow < 1) throw VhError{VH_ERR_ARG, "montage: empty colour table"};
         batch_montage_layout(b);
-        HIP_TRY(hipSetDevice(b->ctx->device));
         const size_t NV = (size_t)b->nb * b->V;
         const int64_t total = b->mt_st[b->nb].off;
         b->d_mt_keys.reserve(6 * (size_t)b->nb);
@@ -1138,16 +1094,14 @@ int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int
         if (proton) b->d_proton.reserve(NV);
         HIP_TRY(hipMemcpyAsync(b->d_mt_parula, parula, sizeof(double) * 3 * prow, hipMemcpyHostToDevice, b->stream));
         if (proton) HIP_TRY(hipMemcpyAsync(b->d_proton, proton, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
-        vh_montage_b_launch(b, proton != nullptr, prow, b->ci_fresh);
-        b->mt_valid = true;
+        vh_montage_b_launch(b, proton != nullptr, prow, b->state.ci_is_fresh());
+        b->state.montage_enqueued();
     })
 }
 
 int vh_batch_download_montage(vh_batch *b, uint8_t *image, int32_t *status) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->mt_valid) throw VhError{VH_ERR_ARG, "vh_batch_montage has not been called since the last run"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+    BATCH_TRY(b, {
+        b->state.need_montage();
         const int64_t total = b->mt_st[b->nb].off;
         if (total > 0 && !image) throw VhError{VH_ERR_ARG, "null buffer"};
         if (total > 0) HIP_TRY(hipMemcpyAsync(image, b->d_mt_img, (size_t)total, hipMemcpyDeviceToHost, b->stream));
@@ -1166,28 +1120,27 @@ static void check_distribution(const vh_batch *b, int norm, int32_t n_bins, floa
         throw VhError{VH_ERR_ARG, "norm must be VH_NORM_MEAN or VH_NORM_P99"};
     if (n_bins < 1 || n_bins > VH_COHORT_BINS) throw VhError{VH_ERR_ARG, "n_bins must be 1..1024"};
     if (!std::isfinite(hi) || !(hi > 0.0f)) throw VhError{VH_ERR_ARG, "hi must be finite and > 0"};
-    if (b && !b->have_result) throw VhError{VH_ERR_ARG, "vh_batch_run has not been called"};
+    if (b) b->state.need_run();
     if (b && !vh_dist_takes(b)) throw VhError{VH_ERR_ARG, "distribution: more than 1900 slices"};
 }
 
 // Enqueue the sweep over what the last run left resident: the N4 volume its chain read, the mask,
 // the LB classes and the defect map as it stands.  It writes its own three buffers only, so nothing
-// another call on the batch reads changes (ci_fresh included).
+// another call on the batch reads changes (the CI stays fresh).
 static void batch_distribution(vh_batch *b, int norm, int32_t n_bins, float hi) {
     b->d_dist_hist.reserve((size_t)b->nb * VH_COHORT_BINS);   // the largest n_bins: no regrowth
     b->d_dist_out.reserve((size_t)b->nb * 2);
     b->d_dist_sl.reserve((size_t)b->nb * b->Z * VH_DIST_COLS);
     const float scale = (float)n_bins / hi;   // once, in float32: the kernel multiplies by it
     vh_dist_launch(b, norm, n_bins, hi, scale);
-    b->dist_bins = n_bins;
-    b->dist_valid = true;
+    b->state.distribution_enqueued(n_bins);
 }
 
 static void batch_download_distribution(vh_batch *b, uint32_t *hist, int64_t *outside, int64_t *slice_counts) {
     hipStream_t st = b->stream;
     const size_t nb = (size_t)b->nb;
     if (hist)
-        HIP_TRY(hipMemcpyAsync(hist, b->d_dist_hist, sizeof(uint32_t) * nb * b->dist_bins, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hist, b->d_dist_hist, sizeof(uint32_t) * nb * b->state.dist_bins(), hipMemcpyDeviceToHost, st));
     if (outside)
         HIP_TRY(hipMemcpyAsync(outside, b->d_dist_out, sizeof(int64_t) * nb * 2, hipMemcpyDeviceToHost, st));
     if (slice_counts)
@@ -1197,20 +1150,15 @@ static void batch_download_distribution(vh_batch *b, uint32_t *hist, int64_t *ou
 }
 
 int vh_batch_distribution(vh_batch *b, int norm, int32_t n_bins, float hi) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         check_distribution(b, norm, n_bins, hi);
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_distribution(b, norm, n_bins, hi);
     })
 }
 
 int vh_batch_download_distribution(vh_batch *b, uint32_t *hist, int64_t *outside, int64_t *slice_counts) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        if (!b->dist_valid)
-            throw VhError{VH_ERR_ARG, "vh_batch_distribution has not been called since the last run"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
+    BATCH_TRY(b, {
+        b->state.need_distribution();
         batch_download_distribution(b, hist, outside, slice_counts);
     })
 }
@@ -1223,43 +1171,21 @@ int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!n4 || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
         check_distribution(nullptr, norm, n_bins, hi);
-        HIP_TRY(hipSetDevice(ctx->device));
-        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
-        if (!vh_dist_takes(b)) throw VhError{VH_ERR_ARG, "distribution: more than 1900 slices"};
-        const size_t NV = (size_t)batch * b->V;
-        HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
-        batch_upload(b, nullptr, mask);
-        vh_run_opts o;
-        vh_default_run_opts(&o);
-        o.do_n4 = 0;
-        o.do_snr = 0;
-        o.do_kmeans = 0;
-        o.thresh = thresh;
-        o.profile = ctx->profile;
-        batch_run(b, o, 2);
+        check_dims(R, C, Z, batch);   // (before the slice count, as the scratch batch checks them)
+        if (Z > VH_DIST_MAX_Z) throw VhError{VH_ERR_ARG, "distribution: more than 1900 slices"};
+        const vh_run_opts o = chain_only_opts(thresh, false, false, ctx->profile);
+        vh_batch *b = run_host_arrays(ctx, nullptr, n4, mask, R, C, Z, batch, o);
         batch_distribution(b, norm, n_bins, hi);
         batch_download_distribution(b, hist, outside, slice_counts);
-        std::vector<VolScalars> sc(batch);
-        HIP_TRY(hipMemcpy(sc.data(), b->d_sc, sizeof(VolScalars) * batch, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < batch; ++i)
-            if (sc[i].n_mask <= 0) throw VhError{VH_ERR_EMPTY, "empty mask"};
+        throw_if_empty_mask(read_scalars(b));
     })
 }
 
 // ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------
-// back where vh_batch_upload leaves a batch: the resident HPvent or the mask statistics and scalars
-// are no longer the last run's, so the calls that read a run's results refuse until the next one
-static void batch_forget_run(vh_batch *b) {
-    b->have_result = false;
-    b->d_n4_last = nullptr;
-    b->km_valid = false;
-    b->sel_valid = false;
-    b->ci_fresh = false;
-    b->mt_layout_valid = false;
-    b->ov_valid = false;
-    b->mt_valid = false;
-    b->dist_valid = false;
-}
+// The resident HPvent, or the mask statistics and scalars, are no longer the last run's: the calls that
+// read a run's results refuse until the next one; an uploaded defect map and an enqueued CI stay.
+// (Not a fresh batch's state, and nothing to do with vh_batch_upload, which invalidates nothing.)
+static void batch_forget_run(vh_batch *b) { b->state.forgot_run(); }
 
 // the mask statistics and the SNR sweep of the resident HPvent, then the Rayleigh estimate of every
 // study from the sweep's noise partials; waits
@@ -1306,28 +1232,22 @@ static void batch_denoise(vh_batch *b, const float *sigma, float strength, int s
 }
 
 int vh_batch_noise_sigma(vh_batch *b, float *sigma) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!sigma) throw VhError{VH_ERR_ARG, "null buffer"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_noise_sigma(b, sigma);
     })
 }
 
 int vh_batch_denoise(vh_batch *b, const float *sigma, float strength, int search_r, int patch_r, int rician) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         check_denoise(sigma, b->nb, strength, search_r, patch_r);
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_denoise(b, sigma, strength, search_r, patch_r, rician);
     })
 }
 
 int vh_batch_download_hp(vh_batch *b, float *hp) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!hp) throw VhError{VH_ERR_ARG, "null buffer"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
         d2h_on_stream(b, hp, b->d_hp, sizeof(float) * (size_t)b->nb * b->V);
     })
 }
@@ -1338,7 +1258,6 @@ int vh_noise_sigma(vh_ctx *ctx, const float *hp, const uint8_t *mask, int64_t R,
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!hp || !mask || !sigma) throw VhError{VH_ERR_ARG, "null buffer"};
-        HIP_TRY(hipSetDevice(ctx->device));
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
         b->profile = ctx->profile != 0;
         batch_upload(b, hp, mask);
@@ -1354,7 +1273,6 @@ int vh_denoise(vh_ctx *ctx, const float *hp, int64_t R, int64_t C, int64_t Z, in
         if (!hp || !out) throw VhError{VH_ERR_ARG, "null buffer"};
         check_dims(R, C, Z, batch);
         check_denoise(sigma, batch, strength, search_r, patch_r);
-        HIP_TRY(hipSetDevice(ctx->device));
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
         b->profile = ctx->profile != 0;
         batch_upload(b, hp, nullptr);
@@ -1423,31 +1341,23 @@ static void batch_download_mask(vh_batch *b, uint8_t *mask, int64_t *count) {
 }
 
 int vh_batch_edit_mask(vh_batch *b, int op, const int32_t *radius) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         check_mask_edit(op, radius, b->nb);
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_edit_mask(b, op, radius);
     })
 }
 
 int vh_batch_paint_mask(vh_batch *b, const uint8_t *strokes, int how) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         if (!strokes) throw VhError{VH_ERR_ARG, "null strokes"};
         if (how < VH_PAINT_OR || how > VH_PAINT_XOR)
             throw VhError{VH_ERR_ARG, "how must be VH_PAINT_OR, _ANDNOT, _AND or _XOR"};
-        HIP_TRY(hipSetDevice(b->ctx->device));
         batch_paint_mask(b, strokes, how);
     })
 }
 
 int vh_batch_download_mask(vh_batch *b, uint8_t *mask, int64_t *count) {
-    if (!b) return VH_ERR_ARG;
-    API_TRY(b->ctx, {
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        batch_download_mask(b, mask, count);
-    })
+    BATCH_TRY(b, { batch_download_mask(b, mask, count); })
 }
 
 int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch, int op,
@@ -1458,7 +1368,6 @@ int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t
         if (!mask) throw VhError{VH_ERR_ARG, "null buffer"};
         check_dims(R, C, Z, batch);
         check_mask_edit(op, radius, batch);
-        HIP_TRY(hipSetDevice(ctx->device));
         vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
         b->profile = ctx->profile != 0;
         batch_upload(b, nullptr, mask);
@@ -2186,10 +2095,9 @@ int vh_comm_init(vh_ctx *ctx, int nranks, int rank, const uint8_t id[VH_COMM_ID_
 }
 
 int vh_batch_cohort_allreduce(vh_batch *b) {
-    API_TRY(b->ctx, {
+    BATCH_TRY(b, {
         vh_ctx *c = b->ctx;
         if (!c->comm) throw VhError{VH_ERR_ARG, "vh_comm_init has not been called"};
-        HIP_TRY(hipSetDevice(c->device));
         if (!c->comm_st) HIP_TRY(hipStreamCreateWithFlags(&c->comm_st, hipStreamNonBlocking));
         if (!b->ev_cpre) HIP_TRY(hipEventCreateWithFlags(&b->ev_cpre, hipEventDisableTiming));
         if (!b->ev_cpost) HIP_TRY(hipEventCreateWithFlags(&b->ev_cpost, hipEventDisableTiming));

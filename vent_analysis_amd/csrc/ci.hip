@@ -526,7 +526,7 @@ int vh_ci_batch_form(const vh_batch *b) {
 
 void vh_ci_expand(vh_batch *b, double *d_ci) {
     const dim3 vg((unsigned)((b->V + VH_TPB - 1) / VH_TPB), (unsigned)b->nb);
-    k_ci_expand16<<<vg, VH_TPB, 0, b->stream>>>(b->d_ci_shell16, b->d_ci_radii, b->ci_nbs, b->ci_minvox, b->V,
+    k_ci_expand16<<<vg, VH_TPB, 0, b->stream>>>(b->d_ci_shell16, b->d_ci_radii, b->state.ci_nbs(), b->state.ci_minvox(), b->V,
                                                 d_ci);
     VH_CHECK_LAUNCH();
 }

@@ -130,11 +130,11 @@ void vh_dist_launch(vh_batch *b, int norm, int n_bins, float hi, float scale) {
     ScopedKTimer tm(b, "dist_b", 7.0 * (double)b->nb * (double)b->V);
     const dim3 grid((unsigned)G, (unsigned)b->nb, 1);
     if (reg)
-        k_dist<true><<<grid, DS_TPB, lds, st>>>(b->d_n4_last, b->d_mask, b->d_defect, b->d_lb, b->d_sc, b->V, Z,
+        k_dist<true><<<grid, DS_TPB, lds, st>>>(b->n4_last(), b->d_mask, b->d_defect, b->d_lb, b->d_sc, b->V, Z,
                                                 norm, n_bins, hi, scale, b->d_dist_hist, b->d_dist_out,
                                                 b->d_dist_sl);
     else
-        k_dist<false><<<grid, DS_TPB, lds, st>>>(b->d_n4_last, b->d_mask, b->d_defect, b->d_lb, b->d_sc, b->V, Z,
+        k_dist<false><<<grid, DS_TPB, lds, st>>>(b->n4_last(), b->d_mask, b->d_defect, b->d_lb, b->d_sc, b->V, Z,
                                                  norm, n_bins, hi, scale, b->d_dist_hist, b->d_dist_out,
                                                  b->d_dist_sl);
     VH_CHECK_LAUNCH();

@@ -320,7 +320,7 @@ void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *
 }
 
 // ---- the montages of a device-resident batch (vh_batch_montage) -------------------------------
-// Everything k_montage reads is resident after vh_batch_run: d_hp, d_n4_last, d_mask, d_defect and
+// Everything k_montage reads is resident after vh_batch_run: d_hp, n4_last(), d_mask, d_defect and
 // (after vh_batch_ci) the int16 shell map with the table's radii.  Three kernels serve the whole
 // batch: k_crop_layout (cropToData of every mask, from the run's mask statistics), k_crop_minmax_b
 // (the crop minima / maxima of proton, HPvent and N4) and k_montage_b (all studies' pixels over their
@@ -589,10 +589,10 @@ void vh_montage_b_launch(vh_batch *b, bool proton, int64_t prow, bool ci_on) {
     MtArgs a{};
     a.st = b->d_mt_st; a.nb = (int32_t)b->nb;
     a.proton = proton ? b->d_proton : nullptr;
-    a.hp = b->d_hp; a.n4 = b->d_n4_last;
+    a.hp = b->d_hp; a.n4 = b->n4_last();
     a.mask = b->d_mask; a.def = b->d_defect;
     a.shell = ci_on ? b->d_ci_shell16 : nullptr;
-    a.radii = b->d_ci_radii; a.nbs = b->ci_nbs; a.minvox = b->ci_minvox;
+    a.radii = b->d_ci_radii; a.nbs = b->state.ci_nbs(); a.minvox = b->state.ci_minvox();
     a.parula = b->d_mt_parula; a.prow = prow;
     a.R = b->R; a.C = b->C; a.Z = b->Z; a.V = b->V;
     a.keys = b->d_mt_keys; a.flag = b->d_mt_flag; a.img = b->d_mt_img;

@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "../../include/vent_hip.h"
+#include "vh_error.h"
+#include "batch_state.h"
 #include "devbuf.h"
 
 #define VH_TPB 256          // threads per block for streaming kernels (4 waves of 64)
@@ -24,11 +26,6 @@
 #define VH_MAX_LEVELS 8
 #define VH_FFT_P 512
 #define VH_MAX_BINS 256
-
-struct VhError {
-    int code;
-    std::string msg;
-};
 
 #define HIP_TRY(expr)                                                                       \
     do {                                                                                    \
@@ -218,10 +215,8 @@ struct vh_batch {
     Buf<float> d_n4;
     Buf<uint8_t> d_defect, d_border, d_lb;
     // vh_batch_select_defect
-    Buf<uint8_t> d_km;               // [nb][V] k-means labels (0 off-mask, else 1 + cluster), on first demand
-    const float *d_n4_last = nullptr;   // (a view) the N4 volume the last run's chain read (d_hp or d_n4)
-    bool km_valid = false;           // d_km holds the last run's labels
-    bool sel_valid = false;          // a selection replaced the last run's maps (VolScalars::n_sel counts it)
+    Buf<uint8_t> d_km;               // [nb][V] k-means labels (0 off-mask, else 1 + cluster), on first demand;
+                                     //   the last run's while state.labels_valid()
     // mask statistics
     Buf<int32_t> d_colrange;         // [nb][CZ][2]  first/last masked row of each (col, slice) column
     Buf<int32_t> d_colcount;         // [nb][CZ]
@@ -292,17 +287,11 @@ struct vh_batch {
     // vh_batch_ci (the CI of the resident defect maps)
     Buf<int16_t> d_ci_shell16;       // [nb][V] shell of each defect voxel, -1 elsewhere
     Buf<uint32_t> d_ci_next;         // [nb][64] (one per 256 bytes) next unclaimed slot of the study's defect list (k_ci_walk_b)
-    Buf<double> d_ci_radii;          // [ci_nbs] the last table's radii: the batch's own copy, so the
-                                     //   float64 map can be expanded after the table is destroyed
-    int64_t ci_nbs = 0;
-    double ci_minvox = 0.0;
-    bool have_defect = false;        // vh_batch_set_defect uploaded the defect maps
-    bool have_ci = false;            // vh_batch_ci has been enqueued
+    Buf<double> d_ci_radii;          // [state.ci_nbs()] the last table's radii: the batch's own copy, so
+                                     //   the float64 map can be expanded after the table is destroyed
     // vh_batch_overlay / vh_batch_montage (export.hip): every buffer on first demand
-    bool ci_fresh = false;           // vh_batch_ci was enqueued after the last change of the resident defect maps
     Buf<uint8_t> d_ov_rgb;           // [nb][Z][R][C][3] the overlay frames
     Buf<uint32_t> d_ov_mm;           // [nb][2] min / max of |N4| (float bits)
-    bool ov_valid = false;           // vh_batch_overlay has been enqueued since the last run
     Buf<float> d_proton;             // [nb][V] the montage's proton volumes
     Buf<int32_t> d_mt_crop;          // [nb][8] k_crop_layout: r0, nr, c0, nc, s0, ns, status, 0
     Buf<MtStudy> d_mt_st;            // [nb + 1]
@@ -310,16 +299,12 @@ struct vh_batch {
     Buf<int32_t> d_mt_flag;          // [nb] 1: a CI colour index reached prow
     Buf<double> d_mt_parula;         // [prow][3], the largest prow so far
     Buf<uint8_t> d_mt_img;           // the compact image buffer
-    std::vector<MtStudy> mt_st;      // host copy of d_mt_st (valid while mt_layout_valid)
+    std::vector<MtStudy> mt_st;      // host copy of d_mt_st (valid while state.layout_is_cached())
     std::vector<int32_t> mt_status;  // [nb] VH_OK / VH_ERR_EMPTY of the layout
-    bool mt_layout_valid = false;    // the layout is the last run's
-    bool mt_valid = false;           // vh_batch_montage has been enqueued since the last run
     // vh_batch_distribution (dist.hip): every buffer on first demand
-    Buf<uint32_t> d_dist_hist;       // [nb][dist_bins] the last call's histograms
+    Buf<uint32_t> d_dist_hist;       // [nb][state.dist_bins()] the last call's histograms
     Buf<unsigned long long> d_dist_out;   // [nb][2] masked voxels below 0 / at or above hi (NaN included)
     Buf<unsigned long long> d_dist_sl;    // [nb][Z][VH_DIST_COLS] slice counts
-    int32_t dist_bins = 0;           // n_bins of the last vh_batch_distribution
-    bool dist_valid = false;         // vh_batch_distribution has been enqueued since the last run
     // vh_batch_denoise / vh_batch_noise_sigma (denoise.hip): on first demand
     Buf<float> d_dn_prm;             // [nb][2] the last denoise's inv_h2 and bias of each study
     Buf<float> d_dn_sigma;           // [nb] the last noise estimate
@@ -339,7 +324,15 @@ struct vh_batch {
     int kst_n = 0;
     // last run options
     vh_run_opts opts{};
-    bool have_result = false;
+    // What of all this is still the last run's: the only record of validity (batch_state.h).  api.hip
+    // alone changes it, through its named transitions.
+    BatchState state;
+    // the N4 volume the last run's chain read, resolved where a kernel is launched: d_hp and d_n4 may
+    // have been exchanged since (vh_batch_denoise), and without a run there is none to hand to a launch
+    const float *n4_last() const {
+        state.need_run();
+        return state.n4_source() == N4Source::n4 ? d_n4.get() : d_hp.get();
+    }
 };
 
 // a compact sphere table resident in HBM (vh_ci_table_create): linear offsets for one (R, C)
