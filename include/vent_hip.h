@@ -49,7 +49,14 @@
  *                erosion, dilation, opening and closing of the resident masks, paint strokes, and the
  *                mask read back with its voxel count (build-defined); kernel-timing class
  *                "mask_edit_b", not listed
- *   vh_pipe_*    the batch pipeline fed from host memory with overlapped transfers (build-defined)
+ *   vh_batch_upload_proton / vh_batch_proton_threshold / vh_batch_segment / vh_batch_mask_overlap /
+ *   vh_otsu / vh_segment
+ *                the "automatic segmentation using proton" item, the last of the reference's list
+ *                (Vent_Analysis.py:1024): an Otsu threshold of the proton image, the dark regions of every
+ *                slice that its border does not reach, and an opening, specified to the byte; and the
+ *                overlap counts against another mask (build-defined); kernel-timing class "segment_b",
+ *                not listed
+ *   vh_pipe_*   the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
 #ifndef VENT_HIP_H
@@ -459,6 +466,81 @@ int vh_batch_paint_mask(vh_batch *b, const uint8_t *strokes /* [nb][V] */, int h
 int vh_batch_download_mask(vh_batch *b, uint8_t *mask /* [nb][V] */, int64_t *count /* [nb] */);  /* both nullable */
 int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch,
                  int op, const int32_t *radius, uint8_t *out, int64_t *count);
+
+/* ---- the lungs from the proton image ("automatic segmentation using proton", Vent_Analysis.py:1024) --
+ * In a proton image the lungs are the dark regions that the bright body encloses.  The mask is made in
+ * four steps -- a threshold, a flood of the dark pixels from the slice border, the dark pixels the
+ * flood did not reach, an opening -- and every step is a max, an integer count or bit logic, so the
+ * result is specified exactly (tests/segment_ref.py is the same in numpy).
+ *
+ * The proton x is float32 [nb][R][C][Z], the slice axis fastest, like HPvent.  It is resident in a
+ * buffer of its own, allocated on the first upload: nb * V * 4 bytes, as much again as the HPvent.
+ * (The montage, when it is given a proton, stores it in that same buffer and so replaces it.)  Every
+ * slice is processed on its own, for the reason given for the denoise filter.
+ *
+ * Statistics, per study.  F is the set of voxels that are finite and >= 0 (-0.0 counts as +0.0).
+ *   pmax   the maximum over F (order-free, hence exact); +0.0 when F is empty
+ *   If pmax is not > 0 the study's threshold is NaN and its histogram is all zeros.  Otherwise
+ *   scale = 256.0f / pmax (one float32 division), and every voxel of F is counted in bin
+ *   min(255, (int)(x * scale)), the product rounded to float32, of a 256-bin uint32 histogram (a product
+ *   that is not below 255 -- an infinite scale times zero included -- counts in bin 255).
+ *
+ * Otsu cut of a histogram h of n_bins >= 2 bins (a host function: no context, no device).  With
+ * N = sum h[i], S = sum i h[i] and, for k = 0 .. n_bins - 2, n0(k) = sum over i <= k of h[i] and
+ * s0(k) = sum over i <= k of i h[i] (all four exact integers, then converted to double): cuts with
+ * n0 == 0 or n0 == N are skipped, and the cut is the lowest k that maximises
+ *   d * d / (n0 * (N - n0)),  d = S * n0 - N * s0,
+ * evaluated in double in exactly this operation order, no operation contracted.  (This is the
+ * between-class variance up to the factor 1 / N^2.)  A histogram with fewer than two occupied bins has
+ * no cut: VH_ERR_EMPTY, and the study's threshold is NaN.
+ *
+ * Threshold.  t = (float)(k + 1) * (pmax / 256.0f): two float32 operations.
+ *
+ * Segmentation of one slice with threshold t.
+ *   dark(r, c) = x < t         (NaN is not dark, -inf is, +inf is not)
+ *   reach      = the dark pixels joined to a dark pixel of the slice's border -- row 0, row R - 1,
+ *                column 0, column C - 1 -- through dark pixels under 4-connectivity
+ *   seg        = dark & ~reach
+ * This is scipy.ndimage.binary_fill_holes(~dark) & dark with scipy's default (cross) structure.  The
+ * fixed point does not depend on the order in which pixels are visited.
+ *
+ * Opening.  Where the study's open_radius k is 1..5, seg becomes open_k(seg) exactly as
+ * vh_batch_edit_mask defines it above: the same discs and the same pads.  Output bytes are 0 / 1.
+ *
+ * vh_batch_upload_proton returns once the proton has left the caller's buffer, as vh_batch_upload does,
+ * and invalidates nothing.  vh_batch_proton_threshold runs the statistics sweep, waits, and returns the
+ * threshold of every study (and pmax and the histograms when asked for); it changes nothing another
+ * call reads.  vh_batch_segment enqueues only: it replaces the resident mask, so the next
+ * vh_batch_run sees the segmentation, and puts the batch back where vh_batch_upload left it, exactly
+ * as vh_batch_edit_mask does; the resident HPvent, N4 and defect maps are not touched.  thresh and
+ * open_radius (NULL: every radius 0) may be reused as soon as the call returns.  VH_ERR_ARG, with
+ * nothing enqueued: a null batch or thresh, no proton resident, any thresh that is not finite or is
+ * <= 0, any radius outside 0..5, a plane of more than 512 rows or 512 columns (and a batch of more than
+ * 65535 studies).  The kernel-timing classes are "segment_b" for the fill and "segment_max_b" and "segment_hist_b"
+ * for the two passes of the sweep (vh_batch_kernel_time reads them; vh_batch_kernel_names does not list them).  The environment
+ * variable VH_SEG_ZC, read at call time, sets how many slices a workgroup of the fill packs into one
+ * bit field (1, 2, 4, 8, 16 or 32, where the plane then fits); the result does not depend on it.
+ *
+ * vh_batch_mask_overlap waits and returns counts[i] = { |resident != 0|, |other != 0|, |both| } of study
+ * i, exact integers counted on the device, from which the Dice and Jaccard indices against a manual
+ * mask are one line.  It stages other in the buffer the paint strokes use, so like a paint it puts the
+ * batch back where vh_batch_upload left it.
+ *
+ * vh_segment is the host-buffer form on the context's scratch batch: thresh NULL takes the Otsu
+ * threshold of every study, and VH_ERR_EMPTY is returned (with thresh_out written, nothing else) when
+ * that is NaN for one of them; mask_out, thresh_out and count are nullable.
+ *
+ * Not done here: connectivity across slices, component size filters, removal of the trachea, learned
+ * segmentation. */
+int vh_batch_upload_proton(vh_batch *b, const float *proton /* [nb][V] */);
+int vh_batch_proton_threshold(vh_batch *b, float *thresh /* [nb] */, float *pmax /* [nb], nullable */,
+                              uint32_t *hist /* [nb][256], nullable */);
+int vh_otsu(const uint32_t *hist, int32_t n_bins, int32_t *cut);
+int vh_batch_segment(vh_batch *b, const float *thresh /* [nb] */, const int32_t *open_radius /* [nb], NULL = all 0 */);
+int vh_batch_mask_overlap(vh_batch *b, const uint8_t *other /* [nb][V] */, int64_t *counts /* [nb][3] */);
+int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z, int64_t batch,
+               const float *thresh, const int32_t *open_radius, uint8_t *mask_out, float *thresh_out,
+               int64_t *count);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

@@ -334,6 +334,31 @@ class Vent_Analysis:
         self.metadata['LungVolume'] = np.sum(self.mask == 1) * np.prod(np.divide(self.vox, 10)) / 1000
         return self.mask
 
+    def segment_mask(self, thresh=None, open_radius=1):
+        """The "automatic segmentation using proton" item of the reference's list (build-defined), on
+        the GPU: ``self.mask`` becomes, slice by slice, the pixels of ``self.proton`` below ``thresh``
+        (None: the Otsu threshold of the proton) that the slice border does not reach through such
+        pixels, opened by the disc of ``open_radius`` pixels (0..5; 0: no opening) -- the spec is in
+        include/vent_hip.h.  ``self.proton`` must be an array of HPvent's shape.  The result is stored
+        in ``self.mask`` as 0/1 in the mask's dtype when there is one, else uint8; ``mask_border`` and
+        ``metadata['LungVolume']`` are recomputed from it, and the new mask is returned.  ``N4HPvent``,
+        ``defectArray`` and the VDP entries of ``metadata`` are left as they are and belong to the old
+        mask until calculate_VDP is run again."""
+        p = self.proton
+        if isinstance(p, str) or np.shape(p) != np.shape(self.HPvent) or np.ndim(p) != 3:
+            raise ValueError("segment_mask: self.proton must be an array of HPvent's shape")
+        old = getattr(self, 'mask', None)
+        dtype = np.asarray(old).dtype if old is not None and not isinstance(old, str) else np.uint8
+        th, rad = _lib._segment_args(thresh, open_radius, 1, np.shape(p))
+        with _lib.pooled_batch(*np.shape(p), 1, device=self.device) as B:
+            B.upload_proton(np.asarray(p, dtype=np.float32)[None])
+            B.segment(th, rad)
+            new = B.download_mask()[0]
+        self.mask = new.astype(dtype)
+        self.mask_border = self.calculateBorder(self.mask)
+        self.metadata['LungVolume'] = np.sum(self.mask == 1) * np.prod(np.divide(self.vox, 10)) / 1000
+        return self.mask
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

@@ -95,6 +95,55 @@ def _mask_edit_args(op, radius, n):
     return op, np.ascontiguousarray(np.broadcast_to(r, (n,)), dtype=np.int32)
 
 
+SEG_MAX_PLANE = 512   # vh_batch_segment takes planes of at most 512 x 512
+
+
+def _segment_args(thresh, open_radius, n, shape=None):
+    """(thresh float32 [n] contiguous or None, open_radius int32 [n] contiguous) for vh_batch_segment:
+    ``thresh`` None (Otsu), a scalar or one value per study, each finite and > 0; ``open_radius`` a
+    scalar or one int per study, each 0..5; ``shape`` (R, C, Z), a plane of at most 512 x 512.
+    ValueError for what the library would refuse, so the message names the argument."""
+    if shape is not None and (shape[0] > SEG_MAX_PLANE or shape[1] > SEG_MAX_PLANE):
+        raise ValueError(f"segment: a plane of at most {SEG_MAX_PLANE} x {SEG_MAX_PLANE}, got {tuple(shape)[:2]}")
+    r = np.asarray(open_radius)
+    if r.dtype == np.bool_ or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"segment: open_radius is an int or one int per study, got {open_radius!r}")
+    if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != n):
+        raise ValueError(f"segment: {n} studies, got open_radius of shape {r.shape}")
+    if r.size and (r.min() < 0 or r.max() > 5):
+        raise ValueError(f"segment: every open_radius must be 0..5, got {open_radius!r}")
+    rad = np.ascontiguousarray(np.broadcast_to(r, (n,)), dtype=np.int32)
+    if thresh is None:
+        return None, rad
+    t = np.asarray(thresh)
+    if t.dtype == np.bool_ or not (np.issubdtype(t.dtype, np.floating) or np.issubdtype(t.dtype, np.integer)):
+        raise ValueError(f"segment: thresh is a number or one per study, got {thresh!r}")
+    if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != n):
+        raise ValueError(f"segment: {n} studies, got thresh of shape {t.shape}")
+    th = np.ascontiguousarray(np.broadcast_to(t.astype(np.float32), (n,)))
+    bad = np.flatnonzero(~(np.isfinite(th) & (th > 0)))
+    if bad.size:
+        raise ValueError(f"segment: every thresh must be finite and > 0 (studies {bad.tolist()}: "
+                         f"{th[bad].tolist()})")
+    return th, rad
+
+
+def otsu(hist):
+    """The Otsu cut of a histogram (vh_otsu, on the host: no device): the lowest k in 0 .. len - 2 that
+    maximises the between-class variance of bins <= k against bins > k.  IndexError when fewer than
+    two bins are occupied."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.ndim != 1 or h.size < 2:
+        raise ValueError("otsu: a 1-D histogram of at least two bins")
+    k = ct.c_int32(-1)
+    rc = lib().vh_otsu(_ptr(h), h.size, ct.byref(k))
+    if rc == VH_ERR_EMPTY:
+        raise IndexError("vh_otsu: fewer than two occupied bins")
+    if rc != VH_OK:
+        raise ValueError(f"vh_otsu: status {rc}")
+    return int(k.value)
+
+
 def denoise_constants(sigma, strength=2.0, patch=1):
     """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
     sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
@@ -198,6 +247,12 @@ _SIGS = {
     "vh_batch_paint_mask": ([_P, _P, ct.c_int], ct.c_int),
     "vh_batch_download_mask": ([_P, _P, _P], ct.c_int),
     "vh_edit_mask": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, _P, _P], ct.c_int),
+    "vh_batch_upload_proton": ([_P, _P], ct.c_int),
+    "vh_batch_proton_threshold": ([_P, _P, _P, _P], ct.c_int),
+    "vh_otsu": ([_P, ct.c_int32, _P], ct.c_int),
+    "vh_batch_segment": ([_P, _P, _P], ct.c_int),
+    "vh_batch_mask_overlap": ([_P, _P, _P], ct.c_int),
+    "vh_segment": ([_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -612,6 +667,24 @@ def edit_mask(mask, op, radius=1, device=0):
     return out
 
 
+def segment(proton, thresh=None, open_radius=1, device=0, count=False):
+    """The lungs from proton images on the host (vh_segment; the spec is in include/vent_hip.h):
+    ``proton`` a 3-D volume or a 4-D batch; ``thresh`` None (the Otsu threshold of every study), a
+    scalar or one value per study; ``open_radius`` 0..5, a scalar or one int per study.  Returns
+    (mask uint8 [B][R][C][Z], the thresholds used float32 [B]), and with ``count`` the voxel counts
+    int64 [B] as a third.  IndexError when Otsu is asked for a study that has no threshold."""
+    c = context(device)
+    x = as_batch(proton, np.float32)
+    B, R, C, Z = x.shape
+    th, rad = _segment_args(thresh, open_radius, B, (R, C, Z))
+    out = np.empty(x.shape, np.uint8)
+    used = np.zeros(B, np.float32)
+    cnt = np.zeros(B, np.int64) if count else None
+    c.check(c.L.vh_segment(c.h, _ptr(x), R, C, Z, B, _ptr(th), _ptr(rad), _ptr(out), _ptr(used), _ptr(cnt)),
+            "vh_segment")
+    return (out, used, cnt) if count else (out, used)
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -1010,6 +1083,55 @@ class Batch:
         cnt = np.zeros(self.shape[0], np.int64) if count else None
         self.ctx.check(self.L.vh_batch_download_mask(self.h, _ptr(out), _ptr(cnt)), "vh_batch_download_mask")
         return (out, cnt) if count else out
+
+    def upload_proton(self, proton):
+        """The proton volumes of the batch, float32 [B][R][C][Z] (vh_batch_upload_proton): resident in
+        a buffer of their own, as large as the HPvent's.  Invalidates nothing."""
+        p = np.ascontiguousarray(proton, dtype=np.float32)
+        if p.shape != self.shape:
+            raise ValueError(f"batch expects {self.shape}")
+        self.ctx.check(self.L.vh_batch_upload_proton(self.h, _ptr(p)), "vh_batch_upload_proton")
+
+    def proton_threshold(self, stats=False):
+        """float32 [B]: the Otsu threshold of each resident proton (vh_batch_proton_threshold; the spec
+        is in include/vent_hip.h), NaN where it is undefined.  With ``stats`` also the maximum it scaled
+        by and the 256-bin histogram it cut: (thresh, pmax float32 [B], hist uint32 [B][256])."""
+        n = self.shape[0]
+        th = np.zeros(n, np.float32)
+        pmax = np.zeros(n, np.float32) if stats else None
+        hist = np.zeros((n, 256), np.uint32) if stats else None
+        self.ctx.check(self.L.vh_batch_proton_threshold(self.h, _ptr(th), _ptr(pmax), _ptr(hist)),
+                       "vh_batch_proton_threshold")
+        return (th, pmax, hist) if stats else th
+
+    def segment(self, thresh=None, open_radius=1):
+        """Enqueue the segmentation of the resident proton (vh_batch_segment; the spec is in
+        include/vent_hip.h): the resident mask becomes, slice by slice, the pixels below ``thresh``
+        that the slice border does not reach through such pixels, opened by the disc of
+        ``open_radius`` (0..5, a scalar or one int per study; 0: no opening).  ``thresh`` is a scalar or
+        one value per study; None takes proton_threshold() first and raises ValueError naming the
+        studies whose threshold is NaN.  The next run() sees the new masks.  After a run, the calls that
+        need a run raise ValueError until the next one.  Returns the thresholds used, float32 [B]."""
+        _segment_args(1.0, open_radius, self.shape[0], self.shape[1:])   # (before any device call)
+        if thresh is None:
+            thresh = self.proton_threshold()
+            if np.isnan(thresh).any():
+                raise ValueError(f"segment: the Otsu threshold is undefined for studies "
+                                 f"{np.flatnonzero(np.isnan(thresh)).tolist()}; pass thresh")
+        th, rad = _segment_args(thresh, open_radius, self.shape[0], self.shape[1:])
+        self.ctx.check(self.L.vh_batch_segment(self.h, _ptr(th), _ptr(rad)), "vh_batch_segment")
+        return th
+
+    def mask_overlap(self, other):
+        """int64 [B][3]: per study the voxels != 0 of the resident mask, of ``other`` ([B][R][C][Z], any
+        dtype) and of both, counted on the device (vh_batch_mask_overlap); Dice is 2 both / (a + b).
+        Like paint_mask it puts the batch back where upload() left it."""
+        o = np.ascontiguousarray(_mask_u8(other), dtype=np.uint8)
+        if o.shape != self.shape:
+            raise ValueError(f"batch expects {self.shape}")
+        cnt = np.zeros((self.shape[0], 3), np.int64)
+        self.ctx.check(self.L.vh_batch_mask_overlap(self.h, _ptr(o), _ptr(cnt)), "vh_batch_mask_overlap")
+        return cnt
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

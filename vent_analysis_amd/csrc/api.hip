@@ -1094,6 +1094,7 @@ int vh_batch_montage(vh_batch *b, const float *proton, const double *parula, int
         if (proton) b->d_proton.reserve(NV);
         HIP_TRY(hipMemcpyAsync(b->d_mt_parula, parula, sizeof(double) * 3 * prow, hipMemcpyHostToDevice, b->stream));
         if (proton) HIP_TRY(hipMemcpyAsync(b->d_proton, proton, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
+        if (proton) b->state.proton_uploaded();   // (the one buffer: it is the resident proton from here on)
         vh_montage_b_launch(b, proton != nullptr, prow, b->state.ci_is_fresh());
         b->state.montage_enqueued();
     })
@@ -1373,6 +1374,177 @@ int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t
         batch_upload(b, nullptr, mask);
         batch_edit_mask(b, op, radius);
         batch_download_mask(b, out, count);
+    })
+}
+
+// ---- the lungs from the proton image of a device-resident batch (segment.hip) -------------------
+// The Otsu cut of a histogram, on the host alone: the lowest k that maximises d * d / (n0 * (N - n0)),
+// d = S * n0 - N * s0, in double and in this operation order.
+int vh_otsu(const uint32_t *hist, int32_t n_bins, int32_t *cut) {
+#pragma clang fp contract(off)
+    if (!hist || !cut || n_bins < 2) return VH_ERR_ARG;
+    uint64_t Ni = 0, Si = 0;
+    int occupied = 0;
+    for (int32_t i = 0; i < n_bins; ++i) {
+        Ni += hist[i];
+        Si += (uint64_t)i * hist[i];
+        occupied += hist[i] != 0;
+    }
+    if (occupied < 2) return VH_ERR_EMPTY;
+    const double N = (double)Ni, S = (double)Si;
+    uint64_t n0i = 0, s0i = 0;
+    double best = -1.0;
+    int32_t at = -1;
+    for (int32_t k = 0; k + 1 < n_bins; ++k) {
+        n0i += hist[k];
+        s0i += (uint64_t)k * hist[k];
+        if (n0i == 0 || n0i == Ni) continue;
+        const double n0 = (double)n0i, s0 = (double)s0i;
+        const double d = S * n0 - N * s0;
+        const double v = d * d / (n0 * (N - n0));
+        if (v > best) { best = v; at = k; }
+    }
+    if (at < 0) return VH_ERR_EMPTY;
+    *cut = at;
+    return VH_OK;
+}
+
+// the argument checks of a segmentation (host only: nothing is enqueued before they pass)
+static void check_segment(const float *thresh, const int32_t *open_radius, int64_t nb) {
+    for (int64_t i = 0; thresh && i < nb; ++i)
+        if (!std::isfinite(thresh[i]) || !(thresh[i] > 0.0f))
+            throw VhError{VH_ERR_ARG, "every thresh must be finite and > 0 (study " + std::to_string(i) + ")"};
+    for (int64_t i = 0; open_radius && i < nb; ++i)
+        if (open_radius[i] < 0 || open_radius[i] > 5)
+            throw VhError{VH_ERR_ARG, "every open_radius must be 0..5 (study " + std::to_string(i) + ")"};
+}
+
+static void batch_upload_proton(vh_batch *b, const float *proton) {
+    const size_t NV = (size_t)b->nb * b->V;
+    b->d_proton.reserve(NV);
+    HIP_TRY(hipMemcpyAsync(b->d_proton, proton, sizeof(float) * NV, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->state.proton_uploaded();
+}
+
+// the statistics sweep, then on the host the Otsu cut and the threshold of every study; waits.  It
+// writes its own two buffers only.
+static void batch_proton_threshold(vh_batch *b, float *thresh, float *pmax, uint32_t *hist) {
+#pragma clang fp contract(off)
+    const size_t nb = (size_t)b->nb;
+    b->d_sg_pmax.reserve(nb);
+    b->d_sg_hist.reserve(nb * 256);
+    vh_proton_stats_launch(b, b->d_proton, b->d_sg_pmax, b->d_sg_hist);
+    std::vector<uint32_t> bits(nb), h(nb * 256);
+    HIP_TRY(hipMemcpyAsync(bits.data(), b->d_sg_pmax, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, b->stream));
+    d2h_on_stream(b, h.data(), b->d_sg_hist, sizeof(uint32_t) * h.size());
+    for (size_t i = 0; i < nb; ++i) {
+        float pm;
+        memcpy(&pm, &bits[i], sizeof(float));
+        int32_t k = 0;
+        float t = std::numeric_limits<float>::quiet_NaN();
+        if (pm > 0.0f && vh_otsu(h.data() + 256 * i, 256, &k) == VH_OK) {
+            const float width = pm / 256.0f;
+            t = (float)(k + 1) * width;
+        }
+        thresh[i] = t;
+        if (pmax) pmax[i] = pm;
+    }
+    if (hist) memcpy(hist, h.data(), sizeof(uint32_t) * h.size());
+}
+
+// Enqueue the fill from d_proton into d_border (free until the next run writes it) and exchange it
+// with d_mask, as batch_edit_mask does; the opening then goes there and back (a study of radius 0 is
+// copied both times).  d_hp, d_n4 and d_defect are not touched.
+static void batch_segment(vh_batch *b, const float *thresh, const int32_t *open_radius) {
+    b->state.need_proton();
+    if (!vh_segment_takes(b)) throw VhError{VH_ERR_ARG, "segment: a plane of at most 512 x 512, at most 65535 studies"};
+    bool open = false;
+    for (int64_t i = 0; open_radius && i < b->nb; ++i) open = open || open_radius[i] > 0;
+    if (open && !vh_mask_edit_takes(b)) throw VhError{VH_ERR_ARG, "segment: batch or tile count out of range"};
+    b->d_sg_thresh.reserve((size_t)b->nb);
+    // (pageable sources: the copies have left thresh and open_radius when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_sg_thresh, thresh, sizeof(float) * (size_t)b->nb, hipMemcpyHostToDevice, b->stream));
+    if (open) {
+        b->d_me_radius.reserve((size_t)b->nb);
+        HIP_TRY(hipMemcpyAsync(b->d_me_radius, open_radius, sizeof(int32_t) * (size_t)b->nb, hipMemcpyHostToDevice,
+                               b->stream));
+    }
+    vh_segment_launch(b, b->d_proton, b->d_border, b->d_sg_thresh);
+    std::swap(b->d_mask, b->d_border);
+    if (open) {
+        vh_mask_morph_launch(b, b->d_mask, b->d_border, b->d_me_radius, 1);
+        vh_mask_morph_launch(b, b->d_border, b->d_mask, b->d_me_radius, 0);
+    }
+    batch_forget_run(b);
+}
+
+// The other mask goes into d_lb (free until the next run writes it), as the strokes of a paint do.
+static void batch_mask_overlap(vh_batch *b, const uint8_t *other, int64_t *counts) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    const size_t nb = (size_t)b->nb;
+    b->d_sg_count.reserve(3 * nb);
+    batch_forget_run(b);   // (d_lb is no longer the run's, whatever follows)
+    HIP_TRY(hipMemcpyAsync(b->d_lb, other, nb * b->V, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_sg_count, 0, sizeof(unsigned long long) * 3 * nb, b->stream));
+    vh_mask_overlap_launch(b, b->d_mask, b->d_lb, b->d_sg_count);
+    d2h_on_stream(b, counts, b->d_sg_count, sizeof(int64_t) * 3 * nb);
+}
+
+int vh_batch_upload_proton(vh_batch *b, const float *proton) {
+    BATCH_TRY(b, {
+        if (!proton) throw VhError{VH_ERR_ARG, "null buffer"};
+        batch_upload_proton(b, proton);
+    })
+}
+
+int vh_batch_proton_threshold(vh_batch *b, float *thresh, float *pmax, uint32_t *hist) {
+    BATCH_TRY(b, {
+        if (!thresh) throw VhError{VH_ERR_ARG, "null buffer"};
+        b->state.need_proton();
+        batch_proton_threshold(b, thresh, pmax, hist);
+    })
+}
+
+int vh_batch_segment(vh_batch *b, const float *thresh, const int32_t *open_radius) {
+    BATCH_TRY(b, {
+        if (!thresh) throw VhError{VH_ERR_ARG, "null thresh"};
+        check_segment(thresh, open_radius, b->nb);
+        batch_segment(b, thresh, open_radius);
+    })
+}
+
+int vh_batch_mask_overlap(vh_batch *b, const uint8_t *other, int64_t *counts) {
+    BATCH_TRY(b, {
+        if (!other || !counts) throw VhError{VH_ERR_ARG, "null buffer"};
+        batch_mask_overlap(b, other, counts);
+    })
+}
+
+int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z, int64_t batch, const float *thresh,
+               const int32_t *open_radius, uint8_t *mask_out, float *thresh_out, int64_t *count) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!proton) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_segment(thresh, open_radius, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        if (!vh_segment_takes(b)) throw VhError{VH_ERR_ARG, "segment: a plane of at most 512 x 512, at most 65535 studies"};
+        batch_upload_proton(b, proton);
+        std::vector<float> th((size_t)batch);
+        if (thresh)
+            std::copy(thresh, thresh + batch, th.begin());
+        else
+            batch_proton_threshold(b, th.data(), nullptr, nullptr);
+        if (thresh_out) std::copy(th.begin(), th.end(), thresh_out);
+        for (int64_t i = 0; i < batch; ++i)
+            if (std::isnan(th[i]))
+                throw VhError{VH_ERR_EMPTY, "segment: no Otsu threshold for study " + std::to_string(i) +
+                                                " (fewer than two occupied bins)"};
+        batch_segment(b, th.data(), open_radius);
+        batch_download_mask(b, mask_out, count);
     })
 }
 

@@ -30,6 +30,8 @@ public:
         bool montage = false;        // vh_batch_montage has been enqueued
         bool distribution = false;   // vh_batch_distribution has been enqueued
         int32_t dist_bins = 0;       // its n_bins (while distribution)
+        // an input, like the resident HPvent and mask: no transition but its own changes it
+        bool proton = false;         // d_proton holds the batch's proton volumes
     };
 
     // ---- transitions.  An uploaded defect map and a present CI survive ran and forgot_run; a cached
@@ -44,6 +46,7 @@ public:
     void layout_cached() { f_.layout = true; }
     void montage_enqueued() { f_.montage = true; }
     void distribution_enqueued(int32_t bins) { f_.distribution = true; f_.dist_bins = bins; }
+    void proton_uploaded() { f_.proton = true; }
 
     // ---- guards: VH_ERR_ARG, for the entry point to raise before it enqueues anything ----
     void need_run() const { need(f_.result, "vh_batch_run has not been called"); }
@@ -60,10 +63,12 @@ public:
     void need_distribution() const {
         need(f_.distribution, "vh_batch_distribution has not been called since the last run");
     }
+    void need_proton() const { need(f_.proton, "no proton resident: vh_batch_upload_proton first"); }
 
     // ---- queries ----
     bool has_run() const { return f_.result; }
     bool layout_is_cached() const { return f_.layout; }
+    bool has_proton() const { return f_.proton; }
     bool ci_is_fresh() const { return f_.ci_fresh; }
     bool selection_on() const { return f_.selection; }
     bool labels_valid() const { return f_.labels; }

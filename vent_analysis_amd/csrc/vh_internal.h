@@ -292,7 +292,8 @@ struct vh_batch {
     // vh_batch_overlay / vh_batch_montage (export.hip): every buffer on first demand
     Buf<uint8_t> d_ov_rgb;           // [nb][Z][R][C][3] the overlay frames
     Buf<uint32_t> d_ov_mm;           // [nb][2] min / max of |N4| (float bits)
-    Buf<float> d_proton;             // [nb][V] the montage's proton volumes
+    Buf<float> d_proton;             // [nb][V] the resident proton volumes (vh_batch_upload_proton, or the
+                                     //   montage's when it is given one), while state.has_proton()
     Buf<int32_t> d_mt_crop;          // [nb][8] k_crop_layout: r0, nr, c0, nc, s0, ns, status, 0
     Buf<MtStudy> d_mt_st;            // [nb + 1]
     Buf<uint32_t> d_mt_keys;         // [nb][6] crop min / max keys of proton, HPvent, N4
@@ -312,6 +313,12 @@ struct vh_batch {
     // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
     Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
     Buf<unsigned long long> d_me_count;   // [nb] voxels != 0 of the resident mask (vh_batch_download_mask)
+    // vh_batch_proton_threshold / vh_batch_segment / vh_batch_mask_overlap (segment.hip): on first
+    // demand.  The fill writes into d_border and the overlap stages the other mask in d_lb, as the edits do
+    Buf<uint32_t> d_sg_pmax;         // [nb] bit pattern of the proton's maximum over its finite voxels >= 0
+    Buf<uint32_t> d_sg_hist;         // [nb][256] the proton histogram behind the Otsu cut
+    Buf<float> d_sg_thresh;          // [nb] the last segmentation's thresholds
+    Buf<unsigned long long> d_sg_count;   // [nb][3] the last overlap counts
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -501,6 +508,15 @@ bool vh_mask_edit_takes(const vh_batch *b);
 void vh_mask_morph_launch(vh_batch *b, const uint8_t *src, uint8_t *dst, const int32_t *d_radius, int erode);
 void vh_mask_paint_launch(vh_batch *b, uint8_t *mask, const uint8_t *strokes, int how);
 void vh_mask_count_launch(vh_batch *b, const uint8_t *mask, unsigned long long *d_cnt);
+// segment.hip: vh_proton_stats_launch: the maximum (as bits) and the 256-bin histogram of every study's
+// proton (both zeroed here).  vh_segment_launch: seg [nb][V] = the dark pixels of every slice that the
+// slice border does not reach, as 0 / 1 bytes, with d_thresh [nb]; vh_segment_takes: the plane is at
+// most 512 x 512 and the grid fits.  vh_mask_overlap_launch: d_cnt [nb][3] (zeroed by the caller) +=
+// |a != 0|, |o != 0|, |both|, a and o [nb][V] from an allocation's start each
+void vh_proton_stats_launch(vh_batch *b, const float *proton, uint32_t *d_pmax_bits, uint32_t *d_hist);
+bool vh_segment_takes(const vh_batch *b);
+void vh_segment_launch(vh_batch *b, const float *proton, uint8_t *seg, const float *d_thresh);
+void vh_mask_overlap_launch(vh_batch *b, const uint8_t *a, const uint8_t *o, unsigned long long *d_cnt);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
