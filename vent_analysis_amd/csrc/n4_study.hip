@@ -90,6 +90,7 @@ struct StudyArgs {
     int32_t nb_ring; // ring rows per wave (<= FIT_NB)
     int32_t o_wx;    // row weights of the current level: Wx[2][R][4] doubles (w^3/sum w^2, w^2)
     int32_t o_wk;    // dense slice weights Wk[2][ncz][Z] (w^3, w^2) of the current level
+    int32_t o_old;   // row tables of the previous level: wx[R] float4, bx[R], xst[kcap] (levels > 0)
     int32_t kcap;    // krange entries per table set
     int64_t vol0;
     double *den;     // [nb][lat_cap] fit denominators of the current level
@@ -214,7 +215,7 @@ __device__ void init_item(const StudyArgs &a, int64_t b, const Item &it, int ite
 }
 
 // wave 0: the first ST_NFIRST masked voxels in raster order (row, then column) and their compact offsets
-__device__ void find_first(const StudyArgs &a, int64_t b, int64_t first, StudyMisc &M) {
+__device__ __forceinline__ void find_first(const StudyArgs &a, int64_t b, int64_t first, StudyMisc &M) {
     const int lane = threadIdx.x & 63;
     int found = 0;
     if (lane == 0) {
@@ -271,8 +272,10 @@ __device__ __forceinline__ float col_T_lds(const double *P1, int i, int ncy, int
 // previous iteration's eval with the tables of its level: the same floats a P1 of the old field
 // would give).  SAME: the previous field uses this level's tables (every
 // iteration but the first of levels > 0), so both windows move together at the row-span
-// boundaries (the old window's next row is loaded one span ahead); otherwise rows are taken one
-// at a time (To: the previous level's row tables, in global memory).
+// boundaries; otherwise To holds the previous level's row tables (LDS, level_begin) and a span ends
+// at the next boundary of either window, after which the window (or both) that reached its boundary
+// moves.  Either way the rows of a span run in prefetched groups and the old window's next row is
+// loaded one span of its own ahead.
 template <bool SAME, int CM>
 __device__ void eval_item(const Item &it, int item, int Z, int CZ, const TabV &Tn, const TabV &To,
                           int ncxn, int ncyn, int ncxo, const double *P1n, float *Tgn, const float *Tgo,
@@ -299,7 +302,7 @@ __device__ void eval_item(const Item &it, int item, int Z, int CZ, const TabV &T
         to1 = told(wbo + 1);
         to2 = told(wbo + 2);
         to3 = told(wbo + 3);
-        if (SAME) to4 = told(wbo + 4);   // (past the last control row: 0 from the range check)
+        to4 = told(wbo + 4);   // (past the last control row: 0 from the range check)
     }
     double sd = 0.0, sd2 = 0.0;
     Range3 rg;
@@ -337,76 +340,60 @@ __device__ void eval_item(const Item &it, int item, int Z, int CZ, const TabV &T
         rg.mx = fmaxf(rg.mx, um);
         r3_ins(rg, un);
     };
-    if (SAME) {
-        int x = it.xs;
+    int x = it.xs;
 #pragma unroll 1
-        for (;;) {
-            const int rb = uni(min(it.xe, Tn.xst[wbn + 1] - 1));
-            // groups of FIT_G rows, two per trip: the next group's L0 loads are in flight while
-            // this group's voxels are evaluated (the span's rows only: the window moves after it)
-            uint32_t oA[FIT_G], oB[FIT_G];
-            int rA[FIT_G], rB[FIT_G];
-            float lA[FIT_G], lB[FIT_G];
-            auto issue = [&](int xb, uint32_t (&o)[FIT_G], int (&r)[FIT_G], float (&l)[FIT_G]) {
+    for (;;) {
+        // the span: the rows up to the next boundary of the new window and (!SAME) of the old one
+        const int xn = uni(Tn.xst[wbn + 1]), xo = SAME ? xn : uni(To.xst[wbo + 1]);
+        const int rb = min(it.xe, min(xn, xo) - 1);
+        // groups of FIT_G rows, two per trip: the next group's L0 loads are in flight while
+        // this group's voxels are evaluated (the span's rows only: the window moves after it)
+        uint32_t oA[FIT_G], oB[FIT_G];
+        int rA[FIT_G], rB[FIT_G];
+        float lA[FIT_G], lB[FIT_G];
+        auto issue = [&](int xb, uint32_t (&o)[FIT_G], int (&r)[FIT_G], float (&l)[FIT_G]) {
 #pragma unroll
-                for (int g = 0; g < FIT_G; ++g) {
-                    const int xg = xb + g;
-                    int rr = 0;
-                    o[g] = item_off(it, xg <= rb ? xg : rb, xg <= rb, CM == 0 ? &rr : nullptr);
-                    r[g] = o[g] == VH_OOB ? (int)VH_OOB : rr * 4;
+            for (int g = 0; g < FIT_G; ++g) {
+                const int xg = xb + g;
+                int rr = 0;
+                o[g] = item_off(it, xg <= rb ? xg : rb, xg <= rb, CM == 0 ? &rr : nullptr);
+                r[g] = o[g] == VH_OOB ? (int)VH_OOB : rr * 4;
 #ifdef AB_EVAL_NOLOAD   // A/B builds only (fixed iteration counts): the phase without its L0 loads
-                    l[g] = 1.0f + (float)g;
+                l[g] = 1.0f + (float)g;
 #else
-                    l[g] = st_load(rL, o[g]);
+                l[g] = st_load(rL, o[g]);
 #endif
-                }
-            };
-            auto run = [&](int xb, const uint32_t (&o)[FIT_G], const int (&r)[FIT_G], const float (&l)[FIT_G]) {
-#pragma unroll
-                for (int g = 0; g < FIT_G; ++g)
-                    voxel(o[g], CM == 0 ? (uint32_t)r[g] : VH_OOB, l[g], xb + g <= rb ? xb + g : rb);
-            };
-            if (x <= rb) {
-                issue(x, oA, rA, lA);
-#pragma unroll 1
-                for (int xb = x;; xb += 2 * FIT_G) {
-                    issue(xb + FIT_G, oB, rB, lB);   // unconditional, as in fit_item
-                    run(xb, oA, rA, lA);
-                    if (xb + FIT_G > rb) break;
-                    issue(xb + 2 * FIT_G, oA, rA, lA);
-                    run(xb + FIT_G, oB, rB, lB);
-                    if (xb + 2 * FIT_G > rb) break;
-                }
             }
-            x = rb + 1 > x ? rb + 1 : x;
-            if (x > it.xe) break;
-            ++wbn;   // next span: both windows move one control row
-            tn0 = tn1; tn1 = tn2; tn2 = tn3;
-            tn3 = tnew(wbn + 3);
-            if (bo_mode) {
-                ++wbo;
-                to0 = to1; to1 = to2; to2 = to3; to3 = to4;
-                to4 = told(wbo + 4);
+        };
+        auto run = [&](int xb, const uint32_t (&o)[FIT_G], const int (&r)[FIT_G], const float (&l)[FIT_G]) {
+#pragma unroll
+            for (int g = 0; g < FIT_G; ++g)
+                voxel(o[g], CM == 0 ? (uint32_t)r[g] : VH_OOB, l[g], xb + g <= rb ? xb + g : rb);
+        };
+        if (x <= rb) {
+            issue(x, oA, rA, lA);
+#pragma unroll 1
+            for (int xb = x;; xb += 2 * FIT_G) {
+                issue(xb + FIT_G, oB, rB, lB);   // unconditional, as in fit_item
+                run(xb, oA, rA, lA);
+                if (xb + FIT_G > rb) break;
+                issue(xb + 2 * FIT_G, oA, rA, lA);
+                run(xb + FIT_G, oB, rB, lB);
+                if (xb + 2 * FIT_G > rb) break;
             }
         }
-    } else {
-#pragma unroll 1
-        for (int x = it.xs; x <= it.xe; ++x) {
-            const int bxn = uni(Tn.bx[x]);
-            while (bxn > wbn) {
-                ++wbn;
-                tn0 = tn1; tn1 = tn2; tn2 = tn3;
-                tn3 = tnew(wbn + 3);
-            }
-            const int bxo = uni(To.bx[x]);
-            while (bo_mode && bxo > wbo) {
-                ++wbo;
-                to0 = to1; to1 = to2; to2 = to3;
-                to3 = told(wbo + 3);
-            }
-            int rr = 0;
-            const uint32_t off = item_off(it, x, true, CM == 0 ? &rr : nullptr);
-            if (off != VH_OOB) voxel(off, (uint32_t)rr * 4u, st_load(rL, off), x);
+        x = rb + 1 > x ? rb + 1 : x;
+        if (x > it.xe) break;
+        // next span: the window whose boundary was reached moves one control row (SAME: both)
+        if (SAME || x >= xn) {
+            ++wbn;
+            tn0 = tn1; tn1 = tn2; tn2 = tn3;
+            tn3 = tnew(wbn + 3);
+        }
+        if (bo_mode && (SAME || x >= xo)) {
+            ++wbo;
+            to0 = to1; to1 = to2; to2 = to3; to3 = to4;
+            to4 = told(wbo + 4);
         }
     }
     if (CM != 0) {
@@ -609,9 +596,24 @@ struct LevelW {
     double2 *Wx3, *Wx2;   // row weights [R][4] doubles (w^3 / sum w^2, w^2; wave-uniform reads)
 };
 
+// The previous level's row tables in LDS (levels > 0): weights [R], window bases [R], span starts
+// [ncx - 2 of that level]
+struct OldRows {
+    float4 *wx;
+    int32_t *bx, *xst;
+};
+__device__ __forceinline__ OldRows old_rows(char *p, int R) {
+    OldRows o;
+    o.wx = reinterpret_cast<float4 *>(p);
+    o.bx = reinterpret_cast<int32_t *>(o.wx + R);
+    o.xst = o.bx + R;
+    return o;
+}
+
 // Stages the level's tables and weights (no barrier: the caller's next one publishes them)
-__device__ __forceinline__ LevelW level_begin(const StudyArgs &a, const DevLevel &lv, char *smem) {
+__device__ __forceinline__ LevelW level_begin(const StudyArgs &a, int L, char *smem) {
     const int t = threadIdx.x;
+    const DevLevel &lv = a.lvs->lv[L];
     LevelW W;
     char *tabp = smem + a.o_tab;
     load_tables(tab_w(tabp, a.R, a.C, a.Z, a.kcap), lv, a.R, a.C, a.Z);
@@ -628,13 +630,27 @@ __device__ __forceinline__ LevelW level_begin(const StudyArgs &a, const DevLevel
     }
     W.Wx3 = reinterpret_cast<double2 *>(smem + a.o_wx);
     W.Wx2 = W.Wx3 + 2 * a.R;
-    for (int x = t; x < a.R; x += ST_TPB) {
+    // (a start index the compiler cannot hoist: the 64-bit byte offset 32 t of these tables was
+    // otherwise computed once per kernel, kept through the level loop, and reloaded from its spill
+    // slot inside eval's row groups, with a wait behind each reload)
+    int xt = t;
+    asm volatile("" : "+v"(xt));
+    for (int x = xt; x < a.R; x += ST_TPB) {
         const double2 *w3 = reinterpret_cast<const double2 *>(lv.ax[0].w3i + 4 * x);
         const double2 *w2 = reinterpret_cast<const double2 *>(lv.ax[0].w2 + 4 * x);
         W.Wx3[2 * x] = w3[0];
         W.Wx3[2 * x + 1] = w3[1];
         W.Wx2[2 * x] = w2[0];
         W.Wx2[2 * x + 1] = w2[1];
+    }
+    if (L > 0) {   // the previous level's row tables, for the eval of this level's first iteration
+        const DevLevel &lo = a.lvs->lv[L - 1];
+        const OldRows o = old_rows(smem + a.o_old, a.R);
+        for (int x = t; x < a.R; x += ST_TPB) {
+            o.wx[x] = *reinterpret_cast<const float4 *>(lo.ax[0].w + 4 * x);
+            o.bx[x] = lo.ax[0].base[x];
+        }
+        for (int i = t; i <= lo.ax[0].ncp - 3; i += ST_TPB) o.xst[i] = lo.xst[i];
     }
     return W;
 }
@@ -646,7 +662,11 @@ __device__ __forceinline__ void fit_pass(const StudyArgs &a, int64_t b, StudyMis
                                          const LevelW &W, const float *Ub, int64_t n, const float *sE, float bmin,
                                          double rinv, FitRing &ring, unsigned long long *numfix,
                                          unsigned long long *fprof = nullptr) {
-    for (int e = threadIdx.x; e < 2 * W.nlat; e += ST_TPB) numfix[e] = 0ull;
+    // (a zero of this pass's own: one 64-bit zero register pair for the whole kernel was reloaded
+    // from its spill slot inside eval's row groups, as the table offset in level_begin was)
+    unsigned long long zero = 0ull;
+    asm volatile("" : "+v"(zero));
+    for (int e = threadIdx.x; e < 2 * W.nlat; e += ST_TPB) numfix[e] = zero;
     if (threadIdx.x == 0) M.item_ctr = 0;
     __syncthreads();
     for (;;) {
@@ -877,18 +897,19 @@ __device__ __forceinline__ void p1_from_lattice(const float *lat, const TabV &T,
 template <class Next>
 __device__ __forceinline__ void eval_pass(const StudyArgs &a, int64_t b, const Next &next, const LevelW &W, int L,
                                           int itk, const double *P1, int tpar, const float *Lb, float *Uo,
-                                          int64_t n, double *ipart, float4 *rp_out) {
+                                          int64_t n, double *ipart, float4 *rp_out, char *smem) {
     float *const Dw = a.D + b * a.VS;
     const bool first_of_level = itk == 1;
     const bool bo_mode = !(L == 0 && first_of_level);
     const bool same = !(first_of_level && L > 0);
-    TabV To = W.T;   // first iteration of a level > 0: the old field's row tables
+    TabV To = W.T;   // first iteration of a level > 0: the old field's row tables (LDS, level_begin)
     int ncxo = W.ncx;
     if (!same) {
-        const DevLevel &lo = a.lvs->lv[L - 1];
-        To.wx = reinterpret_cast<const float4 *>(lo.ax[0].w);
-        To.bx = lo.ax[0].base;
-        ncxo = lo.ax[0].ncp;
+        const OldRows o = old_rows(smem + a.o_old, a.R);
+        To.wx = o.wx;
+        To.bx = o.bx;
+        To.xst = o.xst;
+        ncxo = a.lvs->lv[L - 1].ax[0].ncp;
     }
     float *const Tg0 = a.Tg + (size_t)b * 2 * a.tcap;   // T windows of the last two fields
     float *const Tgn = Tg0 + (size_t)(tpar ^ 1) * a.tcap;
@@ -1012,12 +1033,13 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         for (int e = t; e < nl0; e += ST_TPB) lat[e] = 0.0f;
     }
 #ifdef ST_PROF
-    unsigned long long st_prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = clock64();
+    unsigned long long st_prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = clock64();
+    int st_nfirst = 0, st_nother = 0;   // evals of a level's first iteration (levels > 0) / all others
     if (t == 0) M.fprof[0] = M.fprof[1] = M.fprof[2] = M.fprof[3] = 0ull;
 #endif
     int tpar = 0;   // Tg buffer of the last computed field's T windows
     for (int L = 0; L < a.nlev; ++L) {
-        const LevelW W = level_begin(a, a.lvs->lv[L], smem);
+        const LevelW W = level_begin(a, L, smem);
         // ---- denominator of this level: sum of w^2 over the mask ----
         fit_pass<1>(a, b, M, next, W, a.U + M.uin * a.half + b * a.VS, n, sE, 0.0f, 1.0, ring, numfix);
         ST_MARK(0);
@@ -1069,9 +1091,17 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
             // ---- eval: U into the other buffer, d into D, this field's T windows into Tg ----
             const int uo = (uin + 1) % ST_NB;
             eval_pass(a, b, next, W, L, itk, P1, tpar, Lb, a.U + uo * a.half + b * a.VS, n, ipart,
-                      rpart0 + uo * a.nitems);
+                      rpart0 + uo * a.nitems, smem);
             __syncthreads();
-            ST_MARK(6);
+#ifdef ST_PROF
+            if (itk == 1 && L > 0) {   // eval split: a level's first iteration (levels > 0) apart
+                ST_MARK(11);
+                ++st_nfirst;
+            } else {
+                ST_MARK(6);
+                ++st_nother;
+            }
+#endif
             if (a.conv_mode == 0) {   // S7 on the whole workgroup by guess and verify
                 PcShared<ST_TPB> &PW = *reinterpret_cast<PcShared<ST_TPB> *>(smem + a.o_scr);
                 const float *const Dr = a.D + b * a.VS;
@@ -1128,9 +1158,12 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         printf("ST_PROF b %d n %lld its %d den %llu ctrl %llu hist %llu emap %llu fit %llu latP1 %llu eval %llu "
                "wait %llu level %llu exact %llu top %llu\n",
                ST_PROF_B, (long long)n, its, st_prof[0], st_prof[1], st_prof[2], st_prof[3],
-               st_prof[4], st_prof[5], st_prof[6], st_prof[7], st_prof[8], st_prof[9], st_prof[10]);
+               st_prof[4], st_prof[5], st_prof[6] + st_prof[11], st_prof[7], st_prof[8], st_prof[9], st_prof[10]);
         printf("ST_PROF fit: rows %llu push %llu contract %llu items %llu\n", M.fprof[0], M.fprof[1],
                M.fprof[2], M.fprof[3]);
+        // (the eval figure above is the sum of the two below)
+        printf("ST_PROF eval: first-of-level %llu in %d other %llu in %d\n", st_prof[11], st_nfirst,
+               st_prof[6], st_nother);
     }
 #endif
     // final field's P1 for k_n4_final, from the lattice (the last level's tables are loaded)
@@ -1199,7 +1232,7 @@ __device__ __forceinline__ int next_item_g(StudyMisc &M, const int32_t *ordr, in
 }
 
 // wave 0: this workgroup's items' Range3 merged, as record rrec[u][r]
-__device__ void publish_range(const StudyGrid &g, const float4 *rp, const int32_t *ordr, int nitems, int u,
+__device__ __forceinline__ void publish_range(const StudyGrid &g, const float4 *rp, const int32_t *ordr, int nitems, int u,
                               int r, int G) {
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x;
@@ -1278,7 +1311,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
     uint64_t stg_p[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stg_t0 = wall_clock64();
 #endif
     for (int L = 0; L < a.nlev; ++L) {
-        const LevelW W = level_begin(a, a.lvs->lv[L], smem);
+        const LevelW W = level_begin(a, L, smem);
         // ---- denominators of this level: the previous level's are read by nobody any more (every
         // workgroup passed the last iteration's barriers); level 0's were zeroed by the host ----
         if (L > 0) {
@@ -1357,7 +1390,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_studyg(StudyArgs a, StudyGrid 
             // ---- eval: this workgroup's items; U into the other buffer, d in raster order ----
             const int uo = (uin + 1) % ST_NB;
             eval_pass(a, b, next, W, L, itk, P1, tpar, Lb, a.U + uo * a.half + b * a.VS, n, gd.ipart,
-                      rpart0 + uo * a.nitems);
+                      rpart0 + uo * a.nitems, smem);
             __syncthreads();
             publish_range(gd, rpart0 + uo * a.nitems, ordr, a.nitems, uo, r, G);
             STG_MARK(5);
@@ -1500,6 +1533,8 @@ static bool study_layout(const vh_batch *b, const vh_n4_params &prm, StudyLayout
     a.o_misc = (int32_t)o; o += A(sizeof(StudyMisc));
     a.o_wk = (int32_t)o; o += A(2 * sizeof(double) * (size_t)kcap * Z);
     a.o_wx = (int32_t)o; o += A(2 * 4 * sizeof(double) * (size_t)R);
+    // the previous level's row tables: weights, bases, span starts (level_begin)
+    a.o_old = (int32_t)o; o += A((sizeof(float4) + sizeof(int32_t)) * (size_t)R + sizeof(int32_t) * (size_t)kcap);
     a.o_scr = (int32_t)o; o += A(scr);
     a.o_wave = (int32_t)((fit_num + 15) & ~(size_t)15);   // ring offset inside the scratch
     a.s_cap = s_cap;
