@@ -542,6 +542,89 @@ int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z
                const float *thresh, const int32_t *open_radius, uint8_t *mask_out, float *thresh_out,
                int64_t *count);
 
+/* ---- the proton registered to the xenon image: a rigid integer-voxel shift by mutual information ----
+ * The proton and the xenon volume are acquired in separate breath-holds, so the proton is displaced by
+ * a few voxels in plane and by up to a slice or two through plane; a mask segmented from it inherits the
+ * displacement.  vh_batch_register scores every shift of a small search window by the mutual information
+ * of the two images' joint histogram and picks the best; vh_batch_shift applies a shift to the resident
+ * proton or mask.  The expensive part is one joint histogram per candidate shift -- integer counts, so
+ * it is specified exactly (tests/register_ref.py is the same in numpy); only the score is floating point.
+ *
+ * All volumes are [nb][R][C][Z], the slice axis fastest.  P is the resident proton, X the resident HPvent
+ * as it stands (after a denoise, if one ran).
+ *
+ * Codes.  Per study and per image, F is the set of voxels that are finite and >= 0 (-0.0 counts as +0.0).
+ *   max    the maximum over F; scale = 256.0f / max is one float32 division
+ *   The code of a voxel of F is min(255, (int)(x * scale)) >> 3, the product rounded to float32 (a
+ *   product that is not below 255 -- an infinite scale times zero included -- gives 255 >> 3): 32
+ *   levels.  A voxel outside F is invalid.  For the proton this is the bin of the segment statistics
+ *   above, folded by 8.  A study whose proton max or xenon max is not > 0 is unregistrable: status 1,
+ *   every score NaN, best shift (0, 0, 0), and its histograms are all zeros.
+ *
+ * Joint histogram of a shift s = (dr, dc, dz): J_s[a][b], uint32 [32][32], counts the voxels v for which
+ * v and v + s are both inside the volume, P(v + s) and X(v) are both valid, a is the code of P(v + s)
+ * and b is the code of X(v).  Slices are not processed on their own here: dz couples them.  The counts
+ * do not depend on any order and are exact.
+ *
+ * Search window.  search = (Sr, Sc, Sz) with 0 <= Sr, Sc <= 8, 0 <= Sz <= 2, Sr < R, Sc < C, Sz < Z.  The
+ * shifts are all (dr, dc, dz) with |dr| <= Sr, |dc| <= Sc, |dz| <= Sz, indexed
+ *   i = ((dz + Sz) (2 Sr + 1) + (dr + Sr)) (2 Sc + 1) + (dc + Sc),   ns = (2 Sr + 1)(2 Sc + 1)(2 Sz + 1) <= 1445.
+ *
+ * Score.  With n = sum J, Ja the row sums and Jb the column sums, all exact integers,
+ *   mi = (1 / n) sum over J > 0 of (double)J * log(((double)J * (double)n) / ((double)Ja * (double)Jb))
+ * in double, and mi = 0.0 when n = 0.  Both products are exact in double (they stay below 2^53); where
+ * they are equal the quotient is exactly 1.0 and the term exactly 0.0, so a constant image scores
+ * exactly 0.0 at every shift.  The summation order is free.  vh_mi is this for a [levels][levels]
+ * histogram, 1 <= levels <= 256, on the host (no context, no device).
+ *
+ * Pick.  The best shift has the largest score; among equal scores the smallest |dr| + |dc| + |dz| wins,
+ * then the lowest index i.  A NaN never wins; with nothing but NaN the shift is (0, 0, 0).
+ * vh_register_pick is this for one study's scores [ns], on the host; vh_batch_register picks with it.
+ *
+ * Apply.  Shifting an image A by s gives A'(v) = A(v + s) where v + s is inside the volume and 0
+ * elsewhere.  Shifting the proton by its best shift puts it on the xenon's voxels; the same shift moves a
+ * mask drawn on the proton.
+ *
+ * vh_batch_register needs a resident proton, waits, and returns score [nb][ns], best [nb][3] and, when
+ * asked for, best_score [nb] (the score at best) and status [nb] (0, or 1: unregistrable).  It changes
+ * nothing another call reads: the resident proton, HPvent, mask and a run's results stay as they are.
+ * Its device buffers are allocated on the first call and grow with the window: nb * ns * 4 KiB of
+ * histograms (1.5 GB for 256 studies at the largest window) and two byte volumes of codes.
+ * vh_batch_download_register_hist waits and returns the last call's joint histograms [nb][ns][32][32];
+ * VH_ERR_ARG before any register call.
+ *
+ * vh_batch_shift enqueues only; shift [nb][3] may be reused as soon as the call returns, and every
+ * |component| is at most its dimension (a shift by a whole dimension leaves zeros).  VH_SHIFT_PROTON
+ * replaces the resident proton and invalidates nothing, as vh_batch_upload_proton does.  VH_SHIFT_MASK
+ * replaces the resident mask (bytes are moved as they are), so the next vh_batch_run sees the shifted one,
+ * and puts the batch back where vh_batch_upload left it, exactly as vh_batch_edit_mask does; the resident
+ * HPvent, N4 and defect maps are not touched.  vh_batch_download_proton waits and returns the resident
+ * proton as it stands.
+ *
+ * vh_register is the host-buffer form on the context's scratch batch; status and shifted_out (the
+ * proton shifted by best) are nullable.
+ *
+ * VH_ERR_ARG, with nothing enqueued or changed: a null batch or a null required pointer, no proton
+ * resident (register, VH_SHIFT_PROTON, download_proton), a search outside the limits above, what out of
+ * range, a shift beyond its dimension (and a batch of more than 65535 studies).  The kernel-timing
+ * classes are "register_b" for the joint histograms, "register_score_b" for the scores, "register_codes_b"
+ * for the code pass, "segment_max_b" for the two maximum sweeps and "shift_b" (vh_batch_kernel_time reads
+ * them; vh_batch_kernel_names does not list them).
+ *
+ * Not done here: sub-voxel shifts, rotation, scaling, deformable registration, and protons on a
+ * different grid from the xenon (vh_batch_upload_proton takes the batch's shape only). */
+#define VH_SHIFT_PROTON 0
+#define VH_SHIFT_MASK 1
+int vh_batch_register(vh_batch *b, const int32_t search[3], double *score /* [nb][ns] */, int32_t *best /* [nb][3] */,
+                      double *best_score /* [nb], nullable */, int32_t *status /* [nb], nullable */);
+int vh_batch_download_register_hist(vh_batch *b, uint32_t *hist /* [nb][ns][32][32] */);
+int vh_mi(const uint32_t *joint, int32_t levels, double *mi);
+int vh_register_pick(const double *score, const int32_t search[3], int32_t best[3]);
+int vh_batch_shift(vh_batch *b, int what, const int32_t *shift /* [nb][3] */);
+int vh_batch_download_proton(vh_batch *b, float *proton /* [nb][V] */);
+int vh_register(vh_ctx *ctx, const float *proton, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                const int32_t search[3], double *score, int32_t *best, int32_t *status, float *shifted_out);
+
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,
  * fftshift(fft2(fftshift(K[:, :, k]))) in complex128, then np.transpose(., (1, 0, 2))[:, ::-1, :].

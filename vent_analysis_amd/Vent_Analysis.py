@@ -359,6 +359,32 @@ class Vent_Analysis:
         self.metadata['LungVolume'] = np.sum(self.mask == 1) * np.prod(np.divide(self.vox, 10)) / 1000
         return self.mask
 
+    def register_proton(self, search=(4, 4, 1), apply=True):
+        """Register ``self.proton`` to ``self.HPvent`` (build-defined), on the GPU: every integer shift
+        (dr, dc, dz) with |dr| <= search[0], |dc| <= search[1], |dz| <= search[2] is scored by the mutual
+        information of the two images' 32-level joint histogram -- the spec is in include/vent_hip.h --
+        and the best is returned as ((dr, dc, dz), mi).  ``self.proton`` must be an array of HPvent's
+        shape.  With ``apply`` it is replaced by the shifted array, proton'(v) = proton(v + shift) with
+        zeros where that leaves the volume, in its own dtype, so that it lies on the xenon's voxels (a
+        segment_mask after it draws the mask there).  Nothing else is changed."""
+        p = self.proton
+        if isinstance(p, str) or np.shape(p) != np.shape(self.HPvent) or np.ndim(p) != 3:
+            raise ValueError("register_proton: self.proton must be an array of HPvent's shape")
+        se = _lib._register_args(search, np.shape(p))
+        best, score, _ = _lib.register(np.asarray(p, dtype=np.float32), np.asarray(self.HPvent, dtype=np.float32),
+                                       se, device=self.device)
+        dr, dc, dz = (int(v) for v in best[0])
+        value = float(score[0][dz + se[2], dr + se[0], dc + se[1]])
+        if apply:
+            a = np.asarray(p)
+            out = np.zeros_like(a)
+            R, C, Z = a.shape
+            dst = tuple(slice(max(0, -d), n - max(0, d)) for d, n in zip((dr, dc, dz), (R, C, Z)))
+            src = tuple(slice(max(0, d), n - max(0, -d)) for d, n in zip((dr, dc, dz), (R, C, Z)))
+            out[dst] = a[src]
+            self.proton = out
+        return (dr, dc, dz), value
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

@@ -144,6 +144,72 @@ def otsu(hist):
     return int(k.value)
 
 
+VH_SHIFT_PROTON, VH_SHIFT_MASK = range(2)   # vh_batch_shift targets
+REG_MAX_SEARCH = (8, 8, 2)                  # vh_batch_register: the largest search window
+REG_LEVELS = 32                             # its joint histograms are [32][32]
+
+
+def _register_args(search, shape):
+    """search -> int32 [3] contiguous for vh_batch_register: three ints (Sr, Sc, Sz) with 0 <= Sr, Sc <= 8,
+    0 <= Sz <= 2 and each below its dimension of ``shape`` (R, C, Z).  ValueError for what the library
+    would refuse, so the message names the argument."""
+    s = np.asarray(search)
+    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer) or s.shape != (3,):
+        raise ValueError(f"register: search is three ints (Sr, Sc, Sz), got {search!r}")
+    for k, (v, hi, n) in enumerate(zip(s.tolist(), REG_MAX_SEARCH, tuple(shape)[-3:])):
+        if v < 0 or v > hi or v >= n:
+            raise ValueError(f"register: search[{k}] must be 0..{hi} and below the dimension {n}, got {search!r}")
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def _shift_args(shifts, n, shape):
+    """shifts -> int32 [n][3] contiguous for vh_batch_shift: one (dr, dc, dz) for every study or one per
+    study, each |component| at most its dimension of ``shape`` (R, C, Z)."""
+    s = np.asarray(shifts)
+    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer) or s.shape not in ((3,), (n, 3)):
+        raise ValueError(f"shift: {n} studies take (dr, dc, dz) or one per study, got {shifts!r}")
+    s = np.ascontiguousarray(np.broadcast_to(s, (n, 3)), dtype=np.int32)
+    if s.size and (np.abs(s.astype(np.int64)) > np.asarray(tuple(shape)[-3:], np.int64)).any():
+        raise ValueError(f"shift: every |shift| is at most its dimension of {tuple(shape)[-3:]}, got {shifts!r}")
+    return s
+
+
+def mi(joint):
+    """The mutual information of a square joint histogram (vh_mi, on the host: no device), float64: the
+    sums as exact integers, every term J log((J n) / (Ja Jb)) in double, 0.0 for an empty histogram."""
+    j = np.ascontiguousarray(joint, dtype=np.uint32)
+    if j.ndim != 2 or j.shape[0] != j.shape[1] or not 1 <= j.shape[0] <= 256:
+        raise ValueError("mi: a square histogram of 1..256 levels")
+    out = ct.c_double(0.0)
+    rc = lib().vh_mi(_ptr(j), j.shape[0], ct.byref(out))
+    if rc != VH_OK:
+        raise ValueError(f"vh_mi: status {rc}")
+    return float(out.value)
+
+
+def register_pick(score, search):
+    """The best shift (dr, dc, dz) of one study's scores (vh_register_pick, on the host): the largest
+    score, among equal scores the smallest |dr| + |dc| + |dz|, then the lowest index.  ``score`` is
+    [2Sz+1][2Sr+1][2Sc+1] or flat in that order."""
+    s = np.asarray(search)
+    if s.shape != (3,) or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"register_pick: search is three ints, got {search!r}")
+    se = _register_args(search, (1 << 30,) * 3)
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    ns = int(np.prod(2 * se + 1))
+    if sc.size != ns:
+        raise ValueError(f"register_pick: search {tuple(se.tolist())} has {ns} shifts, got {sc.size} scores")
+    best = np.zeros(3, np.int32)
+    rc = lib().vh_register_pick(_ptr(sc), _ptr(se), _ptr(best))
+    if rc != VH_OK:
+        raise ValueError(f"vh_register_pick: status {rc}")
+    return tuple(int(v) for v in best)
+
+
+def _score_shape(search):
+    return (2 * int(search[2]) + 1, 2 * int(search[0]) + 1, 2 * int(search[1]) + 1)
+
+
 def denoise_constants(sigma, strength=2.0, patch=1):
     """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
     sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
@@ -253,6 +319,13 @@ _SIGS = {
     "vh_batch_segment": ([_P, _P, _P], ct.c_int),
     "vh_batch_mask_overlap": ([_P, _P, _P], ct.c_int),
     "vh_segment": ([_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_register": ([_P, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_download_register_hist": ([_P, _P], ct.c_int),
+    "vh_mi": ([_P, ct.c_int32, ct.POINTER(ct.c_double)], ct.c_int),
+    "vh_register_pick": ([_P, _P, _P], ct.c_int),
+    "vh_batch_shift": ([_P, ct.c_int, _P], ct.c_int),
+    "vh_batch_download_proton": ([_P, _P], ct.c_int),
+    "vh_register": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -683,6 +756,27 @@ def segment(proton, thresh=None, open_radius=1, device=0, count=False):
     c.check(c.L.vh_segment(c.h, _ptr(x), R, C, Z, B, _ptr(th), _ptr(rad), _ptr(out), _ptr(used), _ptr(cnt)),
             "vh_segment")
     return (out, used, cnt) if count else (out, used)
+
+
+def register(proton, hp, search=(4, 4, 1), apply=False, device=0):
+    """The proton registered to the xenon image from host arrays (vh_register; the spec is in
+    include/vent_hip.h): ``proton`` and ``hp`` 3-D volumes or 4-D batches of one shape.  Returns (best int32
+    [B][3], score float64 [B][2Sz+1][2Sr+1][2Sc+1], status int32 [B]), and with ``apply`` the proton
+    shifted by best, float32 [B][R][C][Z], as a fourth."""
+    p = as_batch(proton, np.float32)
+    x = as_batch(hp, np.float32)
+    if p.shape != x.shape:
+        raise ValueError(f"register: proton {p.shape} and hp {x.shape} differ in shape")
+    B, R, C, Z = p.shape
+    se = _register_args(search, (R, C, Z))   # (before any device call)
+    c = context(device)
+    score = np.zeros((B,) + _score_shape(se), np.float64)
+    best = np.zeros((B, 3), np.int32)
+    status = np.zeros(B, np.int32)
+    out = np.empty(p.shape, np.float32) if apply else None
+    c.check(c.L.vh_register(c.h, _ptr(p), _ptr(x), R, C, Z, B, _ptr(se), _ptr(score), _ptr(best), _ptr(status),
+                            _ptr(out)), "vh_register")
+    return (best, score, status, out) if apply else (best, score, status)
 
 
 def ci(defect, table, minvox, device=0, shell=True, out=None):
@@ -1132,6 +1226,46 @@ class Batch:
         cnt = np.zeros((self.shape[0], 3), np.int64)
         self.ctx.check(self.L.vh_batch_mask_overlap(self.h, _ptr(o), _ptr(cnt)), "vh_batch_mask_overlap")
         return cnt
+
+    def register(self, search=(4, 4, 1), hist=False):
+        """Score every shift of the search window of the resident proton against the resident HPvent by
+        mutual information (vh_batch_register; the spec is in include/vent_hip.h) and wait.  Returns
+        (best int32 [B][3], score float64 [B][2Sz+1][2Sr+1][2Sc+1], status int32 [B]: 1 where a study has
+        no voxel > 0 in one of the images, its scores NaN and its shift (0, 0, 0)); with ``hist`` also the
+        joint histograms uint32 [B][2Sz+1][2Sr+1][2Sc+1][32][32].  Changes nothing another call reads."""
+        se = _register_args(search, self.shape[1:])   # (before any device call)
+        n = self.shape[0]
+        score = np.zeros((n,) + _score_shape(se), np.float64)
+        best = np.zeros((n, 3), np.int32)
+        status = np.zeros(n, np.int32)
+        self.ctx.check(self.L.vh_batch_register(self.h, _ptr(se), _ptr(score), _ptr(best), None, _ptr(status)),
+                       "vh_batch_register")
+        if not hist:
+            return best, score, status
+        h = np.zeros(score.shape + (REG_LEVELS, REG_LEVELS), np.uint32)
+        self.ctx.check(self.L.vh_batch_download_register_hist(self.h, _ptr(h)), "vh_batch_download_register_hist")
+        return best, score, status, h
+
+    def shift_proton(self, shifts):
+        """Enqueue a shift of the resident proton (vh_batch_shift): P'(v) = P(v + s) inside the volume, 0
+        elsewhere, ``shifts`` one (dr, dc, dz) or one per study -- register()'s best puts the proton on the
+        xenon's voxels.  Invalidates nothing.  Returns the shifts used, int32 [B][3]."""
+        s = _shift_args(shifts, self.shape[0], self.shape[1:])
+        self.ctx.check(self.L.vh_batch_shift(self.h, VH_SHIFT_PROTON, _ptr(s)), "vh_batch_shift")
+        return s
+
+    def shift_mask(self, shifts):
+        """Enqueue the same shift of the resident masks (bytes move as they are).  The next run() sees
+        the shifted masks; like edit_mask it puts the batch back where upload() left it."""
+        s = _shift_args(shifts, self.shape[0], self.shape[1:])
+        self.ctx.check(self.L.vh_batch_shift(self.h, VH_SHIFT_MASK, _ptr(s)), "vh_batch_shift")
+        return s
+
+    def download_proton(self):
+        """The resident proton as it stands (vh_batch_download_proton), float32 [B][R][C][Z]."""
+        out = np.empty(self.shape, np.float32)
+        self.ctx.check(self.L.vh_batch_download_proton(self.h, _ptr(out)), "vh_batch_download_proton")
+        return out
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

@@ -1548,6 +1548,196 @@ int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z
     })
 }
 
+// ---- the proton registered to the xenon image of a device-resident batch (register.hip) -----------
+// The mutual information of a joint histogram [levels][levels], on the host alone, as k_reg_score
+// evaluates it: sums as exact integers, each term (double)J * log(((double)J * n) / (Ja * Jb)).
+int vh_mi(const uint32_t *joint, int32_t levels, double *mi) {
+#pragma clang fp contract(off)
+    if (!joint || !mi || levels < 1 || levels > 256) return VH_ERR_ARG;
+    const size_t L = (size_t)levels;
+    std::vector<uint64_t> ja(L, 0), jb(L, 0);
+    uint64_t n = 0;
+    for (size_t a = 0; a < L; ++a)
+        for (size_t c = 0; c < L; ++c) {
+            const uint64_t j = joint[a * L + c];
+            ja[a] += j;
+            jb[c] += j;
+            n += j;
+        }
+    double acc = 0.0;
+    for (size_t a = 0; a < L; ++a)
+        for (size_t c = 0; c < L; ++c) {
+            const uint32_t j = joint[a * L + c];
+            if (!j) continue;
+            const double num = (double)j * (double)n;
+            const double den = (double)ja[a] * (double)jb[c];
+            acc += (double)j * std::log(num / den);
+        }
+    *mi = n ? acc / (double)n : 0.0;
+    return VH_OK;
+}
+
+// the limits of a search window that do not depend on the volume
+static bool search_in_limits(const int32_t *search) {
+    return search && search[0] >= 0 && search[0] <= 8 && search[1] >= 0 && search[1] <= 8 && search[2] >= 0 &&
+           search[2] <= 2;
+}
+
+// The best shift of one study's scores [ns]: the largest score; among equal scores the smallest
+// |dr| + |dc| + |dz|, then the lowest index.  A NaN never wins: with nothing but NaN the shift is (0, 0, 0).
+int vh_register_pick(const double *score, const int32_t search[3], int32_t best[3]) {
+    if (!score || !best || !search_in_limits(search)) return VH_ERR_ARG;
+    const int Sr = search[0], Sc = search[1], Sz = search[2];
+    int32_t at[3] = {0, 0, 0};
+    int l1 = -1;
+    double top = 0.0;
+    size_t i = 0;
+    for (int dz = -Sz; dz <= Sz; ++dz)
+        for (int dr = -Sr; dr <= Sr; ++dr)
+            for (int dc = -Sc; dc <= Sc; ++dc, ++i) {
+                const double v = score[i];
+                if (std::isnan(v)) continue;
+                const int d = std::abs(dr) + std::abs(dc) + std::abs(dz);
+                if (l1 < 0 || v > top || (v == top && d < l1)) {
+                    top = v; l1 = d;
+                    at[0] = dr; at[1] = dc; at[2] = dz;
+                }
+            }
+    best[0] = at[0]; best[1] = at[1]; best[2] = at[2];
+    return VH_OK;
+}
+
+// the argument checks of a registration (host only: nothing is enqueued before they pass)
+static void check_register(const int32_t *search, int64_t R, int64_t C, int64_t Z) {
+    if (!search) throw VhError{VH_ERR_ARG, "null search"};
+    if (!search_in_limits(search) || search[0] >= R || search[1] >= C || search[2] >= Z)
+        throw VhError{VH_ERR_ARG, "search must be 0..8, 0..8, 0..2 and below the volume's dimensions"};
+}
+
+static int64_t search_shifts(const int32_t *search) {
+    return (int64_t)(2 * search[0] + 1) * (2 * search[1] + 1) * (2 * search[2] + 1);
+}
+
+// The codes, the joint histogram of every shift and the scores of d_proton against d_hp, then on the
+// host the pick of every study; waits.  It writes its own buffers only.
+static void batch_register(vh_batch *b, const int32_t *search, double *score, int32_t *best, double *best_score,
+                           int32_t *status) {
+    b->state.need_proton();
+    if (!vh_register_takes(b)) throw VhError{VH_ERR_ARG, "register: batch or tile count out of range"};
+    const size_t nb = (size_t)b->nb, NV = nb * (size_t)b->V;
+    const size_t ns = (size_t)search_shifts(search);
+    b->d_rg_max.reserve(2 * nb);
+    b->d_rg_cp.reserve(NV);
+    b->d_rg_cx.reserve(NV);
+    b->d_rg_score.reserve(nb * ns);
+    b->rg_ns = 0;   // (a failed growth leaves no histograms to download)
+    b->d_rg_hist.reserve(nb * ns * 1024);
+    vh_register_launch(b, b->d_proton, b->d_hp, search, b->d_rg_max, b->d_rg_cp, b->d_rg_cx, b->d_rg_hist,
+                       b->d_rg_score);
+    b->rg_ns = (int64_t)ns;
+    std::vector<uint32_t> bits(2 * nb);
+    HIP_TRY(hipMemcpyAsync(bits.data(), b->d_rg_max, sizeof(uint32_t) * 2 * nb, hipMemcpyDeviceToHost, b->stream));
+    d2h_on_stream(b, score, b->d_rg_score, sizeof(double) * nb * ns);
+    for (size_t i = 0; i < nb; ++i) {
+        float pm, xm;
+        memcpy(&pm, &bits[i], sizeof(float));
+        memcpy(&xm, &bits[nb + i], sizeof(float));
+        const bool ok = pm > 0.0f && xm > 0.0f;
+        int32_t *at = best + 3 * i;
+        (void)vh_register_pick(score + ns * i, search, at);
+        if (status) status[i] = ok ? 0 : 1;
+        if (best_score) {
+            const size_t k = ((size_t)(at[2] + search[2]) * (size_t)(2 * search[0] + 1) + (size_t)(at[0] + search[0])) *
+                                 (size_t)(2 * search[1] + 1) + (size_t)(at[1] + search[1]);
+            best_score[i] = score[ns * i + k];
+        }
+    }
+}
+
+static void check_shift(const vh_batch *b, int what, const int32_t *shift) {
+    if (what != VH_SHIFT_PROTON && what != VH_SHIFT_MASK)
+        throw VhError{VH_ERR_ARG, "what must be VH_SHIFT_PROTON or VH_SHIFT_MASK"};
+    if (!shift) throw VhError{VH_ERR_ARG, "null shift"};
+    const int64_t dim[3] = {b->R, b->C, b->Z};
+    for (int64_t i = 0; i < b->nb; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (shift[3 * i + k] > dim[k] || shift[3 * i + k] < -dim[k])
+                throw VhError{VH_ERR_ARG, "every shift must be within the volume's dimensions (study " +
+                                              std::to_string(i) + ")"};
+}
+
+// Enqueue the shift.  The proton goes from d_proton into a volume of its own and the two are exchanged;
+// the mask goes from d_mask into d_border (free until the next run writes it) and is exchanged with it,
+// as batch_edit_mask does.  d_hp, d_n4 and d_defect are not touched.
+static void batch_shift(vh_batch *b, int what, const int32_t *shift) {
+    if (what == VH_SHIFT_PROTON) b->state.need_proton();
+    const size_t nb = (size_t)b->nb;
+    if (what == VH_SHIFT_PROTON) b->d_rg_ptmp.reserve(nb * (size_t)b->V);
+    b->d_rg_shift.reserve(3 * nb);
+    // (pageable source: the copy has left shift when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_rg_shift, shift, sizeof(int32_t) * 3 * nb, hipMemcpyHostToDevice, b->stream));
+    if (what == VH_SHIFT_PROTON) {
+        vh_shift_launch_f32(b, b->d_proton, b->d_rg_ptmp, b->d_rg_shift);
+        std::swap(b->d_proton, b->d_rg_ptmp);
+    } else {
+        vh_shift_launch_u8(b, b->d_mask, b->d_border, b->d_rg_shift);
+        std::swap(b->d_mask, b->d_border);
+        batch_forget_run(b);
+    }
+}
+
+int vh_batch_register(vh_batch *b, const int32_t search[3], double *score, int32_t *best, double *best_score,
+                      int32_t *status) {
+    BATCH_TRY(b, {
+        if (!score || !best) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_register(search, b->R, b->C, b->Z);
+        batch_register(b, search, score, best, best_score, status);
+    })
+}
+
+int vh_batch_download_register_hist(vh_batch *b, uint32_t *hist) {
+    BATCH_TRY(b, {
+        if (!hist) throw VhError{VH_ERR_ARG, "null buffer"};
+        if (b->rg_ns <= 0) throw VhError{VH_ERR_ARG, "vh_batch_register has not been called"};
+        d2h_on_stream(b, hist, b->d_rg_hist, sizeof(uint32_t) * (size_t)b->nb * (size_t)b->rg_ns * 1024);
+    })
+}
+
+int vh_batch_shift(vh_batch *b, int what, const int32_t *shift) {
+    BATCH_TRY(b, {
+        check_shift(b, what, shift);
+        batch_shift(b, what, shift);
+    })
+}
+
+int vh_batch_download_proton(vh_batch *b, float *proton) {
+    BATCH_TRY(b, {
+        if (!proton) throw VhError{VH_ERR_ARG, "null buffer"};
+        b->state.need_proton();
+        d2h_on_stream(b, proton, b->d_proton, sizeof(float) * (size_t)b->nb * b->V);
+    })
+}
+
+int vh_register(vh_ctx *ctx, const float *proton, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                const int32_t search[3], double *score, int32_t *best, int32_t *status, float *shifted_out) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!proton || !hp || !score || !best) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_register(search, R, C, Z);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, hp, nullptr);
+        batch_upload_proton(b, proton);
+        batch_register(b, search, score, best, nullptr, status);
+        if (shifted_out) {
+            batch_shift(b, VH_SHIFT_PROTON, best);
+            d2h_on_stream(b, shifted_out, b->d_proton, sizeof(float) * (size_t)batch * b->V);
+        }
+    })
+}
+
 // ---- TWIX recon (recon.hip) -------------------------------------------------------------------
 int vh_recon(vh_ctx *ctx, const double *k, int64_t n0, int64_t n1, int64_t nz, double *out) {
     API_TRY(ctx, {

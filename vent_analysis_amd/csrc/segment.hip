@@ -83,6 +83,15 @@ __global__ void __launch_bounds__(SG_TPB) k_seg_hist(const float *__restrict__ x
     kst_end(ks);
 }
 
+// the maximum sweep alone (d_max_bits zeroed by the caller): the registration takes it for both images
+void vh_seg_max_launch(vh_batch *b, const float *x, uint32_t *d_max_bits) {
+    if (b->nb > 65535) throw VhError{VH_ERR_ARG, "more than 65535 studies"};   // (grid y)
+    const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((b->V + SG_TPB * 128 - 1) / (SG_TPB * 128), 32));
+    ScopedKTimer tm(b, "segment_max_b", 4.0 * (double)b->nb * (double)b->V, true);
+    k_seg_max<<<dim3((unsigned)chunks, (unsigned)b->nb, 1), SG_TPB, 0, b->stream>>>(x, b->V, d_max_bits, tm.stamp());
+    VH_CHECK_LAUNCH();
+}
+
 void vh_proton_stats_launch(vh_batch *b, const float *proton, uint32_t *d_pmax_bits, uint32_t *d_hist) {
     static_assert(SG_TPB == 256, "one thread per histogram bin");
     const size_t nb = (size_t)b->nb;
@@ -93,11 +102,7 @@ void vh_proton_stats_launch(vh_batch *b, const float *proton, uint32_t *d_pmax_b
     // 0.38 + 0.31 ms, workgroups ending as soon as they had started
     const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((b->V + SG_TPB * 128 - 1) / (SG_TPB * 128), 32));
     const dim3 grid((unsigned)chunks, (unsigned)b->nb, 1);
-    {
-        ScopedKTimer tm(b, "segment_max_b", 4.0 * (double)b->nb * (double)b->V, true);
-        k_seg_max<<<grid, SG_TPB, 0, b->stream>>>(proton, b->V, d_pmax_bits, tm.stamp());
-        VH_CHECK_LAUNCH();
-    }
+    vh_seg_max_launch(b, proton, d_pmax_bits);
     ScopedKTimer tm(b, "segment_hist_b", 4.0 * (double)b->nb * (double)b->V, true);
     k_seg_hist<<<grid, SG_TPB, 0, b->stream>>>(proton, b->V, d_pmax_bits, d_hist, tm.stamp());
     VH_CHECK_LAUNCH();

@@ -319,6 +319,14 @@ struct vh_batch {
     Buf<uint32_t> d_sg_hist;         // [nb][256] the proton histogram behind the Otsu cut
     Buf<float> d_sg_thresh;          // [nb] the last segmentation's thresholds
     Buf<unsigned long long> d_sg_count;   // [nb][3] the last overlap counts
+    // vh_batch_register / vh_batch_shift (register.hip): on first demand, and nothing another call reads
+    Buf<uint32_t> d_rg_max;          // [2][nb] bit patterns of the proton's and the HPvent's maxima over F
+    Buf<uint8_t> d_rg_cp, d_rg_cx;   // [nb][V] the 32-level codes of the proton and of the HPvent, 255 invalid
+    Buf<uint32_t> d_rg_hist;         // [nb][rg_ns][32][32] the last register call's joint histograms
+    Buf<double> d_rg_score;          // [nb][rg_ns] its scores
+    int64_t rg_ns = 0;               // its shifts; 0 before any register call
+    Buf<int32_t> d_rg_shift;         // [nb][3] the last shift call's shifts
+    Buf<float> d_rg_ptmp;            // [nb][V] the proton shift's destination, exchanged with d_proton
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -517,6 +525,19 @@ void vh_proton_stats_launch(vh_batch *b, const float *proton, uint32_t *d_pmax_b
 bool vh_segment_takes(const vh_batch *b);
 void vh_segment_launch(vh_batch *b, const float *proton, uint8_t *seg, const float *d_thresh);
 void vh_mask_overlap_launch(vh_batch *b, const uint8_t *a, const uint8_t *o, unsigned long long *d_cnt);
+// the maximum sweep of segment.hip alone: d_max_bits [nb] (zeroed by the caller) = the bit pattern of
+// every study's maximum over its finite voxels >= 0; timing class "segment_max_b"
+void vh_seg_max_launch(vh_batch *b, const float *x, uint32_t *d_max_bits);
+// register.hip: vh_register_launch: the maxima (d_maxb [2][nb]), the codes (d_cp, d_cx [nb][V]), the
+// joint histogram of every shift of the search window (d_hist [nb][ns][32][32], zeroed here) and the
+// scores (d_score [nb][ns]) of proton against hp; vh_register_takes: the grid fits.
+// vh_shift_launch_*: dst(v) = src(v + shift[study]) inside the volume, 0 elsewhere, d_shift [nb][3]
+bool vh_register_takes(const vh_batch *b);
+void vh_register_launch(vh_batch *b, const float *proton, const float *hp, const int32_t search[3],
+                        uint32_t *d_maxb, uint8_t *d_cp, uint8_t *d_cx, uint32_t *d_hist, double *d_score);
+void vh_register_score_launch(vh_batch *b, const uint32_t *d_hist, const uint32_t *d_maxb, int ns, double *d_score);
+void vh_shift_launch_f32(vh_batch *b, const float *src, float *dst, const int32_t *d_shift);
+void vh_shift_launch_u8(vh_batch *b, const uint8_t *src, uint8_t *dst, const int32_t *d_shift);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
