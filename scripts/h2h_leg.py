@@ -58,7 +58,6 @@ def main():
     h["torch"] = a.torch
     h["warm_device"] = a.warm_device
     h["cpu_load"] = a.cpu_load
-    h["d2h_late"] = os.environ.get("VH_PIPE_D2H_LATE", "0")
     print(json.dumps(h), flush=True)
     if Bt:
         Bt.close()

@@ -25,7 +25,7 @@ from vent_analysis_amd._lib import COHORT_BINS, COMM_ID_BYTES, empty_aligned  # 
 
 LIB_PATH = None          # no shared object: bench.lib_digest() gives None, no PMC summary matches
 COMM_KIND = "gloo stand-in (tests/standin_lib.py, --dry-run)"
-PIN_NODE_BUDGET = 32 << 30   # vh_pipe's default page-locking budget per node (api.hip)
+PIN_NODE_BUDGET = 32 << 30   # vh_pipe's default page-locking budget per node (pipe.hip)
 
 # synthetic kernel-class timings per run (ms per launch, launches per run): a multi-launch class
 # whose time per step exceeds that of the class with the longest single launch, so the line's
@@ -162,7 +162,7 @@ class Batch:
 
 class Pipe:
     """vh_pipe's host side as far as bench.host_to_host sees it: copies through and the
-    page-locking budget rule of vh_pipe_run (api.hip: VH_PIPE_PIN_CAP, else 32 GiB per node divided
+    page-locking budget rule of vh_pipe_run (pipe.hip: VH_PIPE_PIN_CAP, else 32 GiB per node divided
     by LOCAL_WORLD_SIZE): the caller bytes past the budget count as staged ranges."""
 
     def __init__(self, R, C, Z, sub, slots=3, device=0):

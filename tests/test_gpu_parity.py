@@ -345,6 +345,37 @@ def test_pipe_pin_budget_stages_the_rest(monkeypatch):
         assert np.array_equal(a, b)
 
 
+def test_pipe_staged_path_equals_pinned_path(monkeypatch):
+    """VH_PIPE_STAGE=1 pins no caller page: the 0 / 1 mask crosses as bytes and every range (3 MB of
+    image per chunk, above the 1 MiB pinning floor; the last chunk ragged) goes through the pinned
+    staging, with the results of the run that pins in place."""
+    R, C, Z = 128, 128, 24
+    n, sub, slots = 5, 2, 2
+    hp, mk = synth_batch(R, C, Z, n, base_seed=123)
+    o = _lib.Batch.options(do_n4=True, vox=(1.5, 1.5, 10.0))
+    monkeypatch.delenv("VH_PIPE_STAGE", raising=False)
+    P = _lib.Pipe(R, C, Z, sub, slots=slots)
+    ref = P.run(hp, mk, o)
+    peak0, _ = P.stats()
+    P.close()
+    assert peak0 > 0
+    monkeypatch.setenv("VH_PIPE_STAGE", "1")
+    P = _lib.Pipe(R, C, Z, sub, slots=slots)
+    got = P.run(hp, mk, o)
+    peak, staged = P.stats()
+    P.close()
+    assert peak == 0 and staged > 0
+    for a, b in zip(got[:4], ref[:4]):
+        assert np.array_equal(a, b)
+    for r, q in zip(got[4], ref[4]):
+        assert [r.vdp, r.vdp_lb, r.n_km0] + list(r.n4_iters[:4]) == \
+            [q.vdp, q.vdp_lb, q.n_km0] + list(q.n4_iters[:4])
+
+
+def test_pipe_run_null_handle_is_an_argument_error():
+    assert _lib.lib().vh_pipe_run(None, None, None, 1, None, None, None, None, None, None) == _lib.VH_ERR_ARG
+
+
 def test_batch_equals_single():
     hp, mk = synth_batch(64, 64, 16, 4, base_seed=3)
     B = _lib.Batch(64, 64, 16, 4)

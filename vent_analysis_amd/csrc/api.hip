@@ -14,10 +14,6 @@
 #include <limits>
 #include <stdexcept>
 
-#ifndef VH_COPY_THREADS
-#define VH_COPY_THREADS 8   // host threads per staging copy (each pipe slot copies on its own)
-#endif
-
 #include "vh_internal.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -112,36 +108,13 @@ static void timer_totals(vh_batch *b, const char *name, double *total_ms, int64_
 // ---------------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------------
-static int fail(vh_ctx *c, int code, const std::string &msg) {
+int vh_fail(vh_ctx *c, int code, const std::string &msg) {
     if (c) {
         std::lock_guard<std::mutex> g(c->err_mu);
         c->last_error = msg;
     }
     return code;
 }
-
-#define API_TRY(ctx, ...)                                                                    \
-    try {                                                                                    \
-        __VA_ARGS__                                                                          \
-    } catch (const VhError &e) {                                                             \
-        return fail(ctx, e.code, e.msg);                                                     \
-    } catch (const std::bad_alloc &) {                                                       \
-        return fail(ctx, VH_ERR_NOMEM, "host allocation failed");                            \
-    } catch (const std::exception &e) {                                                      \
-        return fail(ctx, VH_ERR_HIP, e.what());                                              \
-    } catch (...) {                                                                          \
-        return fail(ctx, VH_ERR_HIP, "unknown error");                                       \
-    }                                                                                        \
-    return VH_OK;
-
-// Every vh_batch_* entry point but vh_batch_destroy: a null handle is VH_ERR_ARG; otherwise API_TRY on
-// the batch's context, with its device current.
-#define BATCH_TRY(b, ...)                                                                    \
-    if (!(b)) return VH_ERR_ARG;                                                             \
-    API_TRY((b)->ctx, {                                                                      \
-        HIP_TRY(hipSetDevice((b)->ctx->device));                                             \
-        __VA_ARGS__                                                                          \
-    })
 
 // Buf's allocator (devbuf.h): the library's only device and pinned-host allocations, but for
 // vh_host_alloc / vh_host_free, whose memory the caller owns
@@ -169,7 +142,7 @@ static void check_dims(int64_t R, int64_t C, int64_t Z, int64_t batch) {
         throw VhError{VH_ERR_ARG, "volume dims out of range"};
 }
 
-static void batch_free(vh_batch *b) {
+void vh_free_batch(vh_batch *b) {
     if (!b) return;
     b->kst_n = 0;   // no stamp reset: nothing is enqueued on the drained stream
     clear_timers(b);
@@ -182,7 +155,7 @@ static void batch_free(vh_batch *b) {
     delete b;   // the buffers (every caller has drained the batch's stream)
 }
 
-static vh_batch *batch_new(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t nb) {
+vh_batch *vh_new_batch(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t nb) {
     check_dims(R, C, Z, nb);
     HIP_TRY(hipSetDevice(ctx->device));
     vh_batch *b = new vh_batch;
@@ -258,7 +231,7 @@ static vh_batch *batch_new(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t
         if (b->d_cohort.reserve((size_t)VH_COHORT_BINS))
             HIP_TRY(hipMemset(b->d_cohort, 0, sizeof(uint64_t) * VH_COHORT_BINS));
     } catch (...) {
-        batch_free(b);
+        vh_free_batch(b);
         throw;
     }
     return b;
@@ -287,7 +260,7 @@ static void check_n4_params(const vh_batch *b, const vh_n4_params &p) {
 }
 
 // n4_src: 0 = run N4 from d_hp, 1 = identity (d_hp), 2 = caller-uploaded d_n4
-static void batch_run(vh_batch *b, const vh_run_opts &o, int n4_src) {
+void vh_run_batch(vh_batch *b, const vh_run_opts &o, int n4_src) {
     HIP_TRY(hipSetDevice(b->ctx->device));
     b->profile = o.profile != 0;
     b->opts = o;
@@ -337,7 +310,7 @@ static void throw_if_empty_mask(const std::vector<VolScalars> &sc, bool with_snr
 }
 
 // per-study results from host copies of the scalars (and N4 states when the batch ran N4)
-static void fill_results_from(const vh_batch *b, const VolScalars *sc, const N4State *st, vh_vdp_result *res) {
+void vh_fill_results(const vh_batch *b, const VolScalars *sc, const N4State *st, vh_vdp_result *res) {
     if (b->opts.do_n4) check_n4_watchdog(st, b->nb);
     const double *vox = b->opts.vox;
     // np.prod(np.divide(vox, 10)): sequential multiply (Vent_Analysis.py:166, 252)
@@ -381,22 +354,8 @@ static std::vector<VolScalars> batch_download(vh_batch *b, float *n4, uint8_t *d
     if (!res) return {};
     const std::vector<VolScalars> sc = read_scalars(b);
     const std::vector<N4State> n4st = b->opts.do_n4 ? read_n4_states(b) : std::vector<N4State>();
-    fill_results_from(b, sc.data(), n4st.data(), res);
+    vh_fill_results(b, sc.data(), n4st.data(), res);
     return sc;
-}
-
-static void pipe_free(vh_pipe *p) {
-    if (!p) return;
-    for (auto &q : p->slot) {
-        if (q.b) {
-            (void)hipStreamSynchronize(q.b->stream);
-            batch_free(q.b);
-        }
-        if (q.done) (void)hipEventDestroy(q.done);
-        if (q.h2d) (void)hipEventDestroy(q.h2d);
-        if (q.packed) (void)hipEventDestroy(q.packed);
-    }
-    delete p;   // the slots' staging buffers
 }
 
 // The context's cached scratch batch for the host-buffer entry points (caller holds ctx->mu), with
@@ -407,10 +366,10 @@ static vh_batch *scratch_batch(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int
     if (s && s->R == R && s->C == C && s->Z == Z && s->nb == nb) return s;
     if (s) {
         (void)hipStreamSynchronize(s->stream);
-        batch_free(s);
+        vh_free_batch(s);
     }
     s = nullptr;
-    s = batch_new(ctx, R, C, Z, nb);
+    s = vh_new_batch(ctx, R, C, Z, nb);
     return s;
 }
 
@@ -433,7 +392,7 @@ static vh_batch *run_host_arrays(vh_ctx *ctx, const float *hp, const float *n4, 
     vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
     HIP_TRY(hipMemcpyAsync(b->d_n4, n4, sizeof(float) * (size_t)batch * b->V, hipMemcpyHostToDevice, b->stream));
     batch_upload(b, hp, mask);
-    batch_run(b, o, 2);
+    vh_run_batch(b, o, 2);
     return b;
 }
 
@@ -510,7 +469,7 @@ int vh_destroy(vh_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->scratch) {
         (void)hipStreamSynchronize(ctx->scratch->stream);
-        batch_free(ctx->scratch);
+        vh_free_batch(ctx->scratch);
         ctx->scratch = nullptr;
     }
     if (ctx->comm) ncclCommDestroy((ncclComm_t)ctx->comm);
@@ -720,14 +679,14 @@ int vh_ci_tab(vh_ctx *ctx, const uint8_t *defect, int64_t R, int64_t C, int64_t 
 
 int vh_batch_create(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t batch, vh_batch **out) {
     *out = nullptr;
-    API_TRY(ctx, { *out = batch_new(ctx, R, C, Z, batch); })
+    API_TRY(ctx, { *out = vh_new_batch(ctx, R, C, Z, batch); })
 }
 
 int vh_batch_destroy(vh_batch *b) {
     if (b) {
         (void)hipSetDevice(b->ctx->device);
         (void)hipStreamSynchronize(b->stream);
-        batch_free(b);
+        vh_free_batch(b);
     }
     return VH_OK;
 }
@@ -739,7 +698,7 @@ int vh_batch_upload(vh_batch *b, const float *hp, const uint8_t *mask) {
 int vh_batch_run(vh_batch *b, const vh_run_opts *opts) {
     BATCH_TRY(b, {
         if (!opts) throw VhError{VH_ERR_ARG, "null options"};
-        batch_run(b, *opts, opts->do_n4 ? 0 : 1);
+        vh_run_batch(b, *opts, opts->do_n4 ? 0 : 1);
     })
 }
 
@@ -1759,594 +1718,6 @@ int vh_recon(vh_ctx *ctx, const double *k, int64_t n0, int64_t n1, int64_t nz, d
     })
 }
 
-// ---- host-to-host pipeline -----
-// pageable <-> pinned staging copies split over host threads: one thread's memcpy (~5-10 GB/s) bounded
-// the whole pipeline at about half the device-resident rate; the copy engines and the
-// PCIe link are far from busy at that rate
-// The three u8 maps of a pipe chunk leave the GPU as one byte per voxel, defect | border << 1 |
-// LB class << 2 (0/1, 0/1, 0..6): PCIe carries H2D and D2H together at ~53 GB/s on the box
-// (scripts/dev/h2h_probe.py, both directions at once), so the host-to-host rate is link-bound
-// near the device rate; this takes 12 -> 10 bytes per voxel.  The slot's host threads unpack.
-__global__ void k_pack_maps(const uint8_t *__restrict__ d, const uint8_t *__restrict__ b,
-                            const uint8_t *__restrict__ l, uint8_t *__restrict__ out, int64_t n,
-                            const uint32_t *__restrict__ sc, int64_t sc_words,
-                            const uint32_t *__restrict__ st, int64_t st_words, uint32_t *__restrict__ scal) {
-    // the chunk's scalars and N4 states ahead of the maps (the D2H block's head)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < sc_words + st_words;
-         i += (int64_t)gridDim.x * blockDim.x)
-        scal[i] = i < sc_words ? sc[i] : st[i - sc_words];
-    const int64_t n16 = n / 16;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint4 vd = reinterpret_cast<const uint4 *>(d)[i], vb = reinterpret_cast<const uint4 *>(b)[i],
-                    vl = reinterpret_cast<const uint4 *>(l)[i];
-        uint4 o;   // bytes pack lane-wise: no carries (defect, border <= 1, class <= 6)
-        o.x = vd.x | (vb.x << 1) | (vl.x << 2);
-        o.y = vd.y | (vb.y << 1) | (vl.y << 2);
-        o.z = vd.z | (vb.z << 1) | (vl.z << 2);
-        o.w = vd.w | (vb.w << 1) | (vl.w << 2);
-        reinterpret_cast<uint4 *>(out)[i] = o;
-    }
-    for (int64_t i = n16 * 16 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = (uint8_t)(d[i] | (b[i] << 1) | (l[i] << 2));
-}
-
-static void par_memcpy(void *dst, const void *src, size_t bytes);
-
-// studies cnt .. sub - 1 of a ragged pipe chunk := study cnt - 1 (image and mask)
-__global__ void k_repeat_last(float *hp, uint8_t *mask, int64_t V, int64_t cnt, int64_t sub) {
-    const int64_t n = (sub - cnt) * V;
-    const float *sh = hp + (cnt - 1) * V;
-    const uint8_t *sm = mask + (cnt - 1) * V;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t v = i % V;
-        hp[cnt * V + i] = sh[v];
-        mask[cnt * V + i] = sm[v];
-    }
-}
-
-// The mask crosses PCIe as one bit per voxel (bit i % 8 of byte i / 8); k_unpack_mask restores the
-// bytes on the device.  par_pack_mask returns false (nothing usable) if a byte is not 0 / 1.
-__global__ void k_unpack_mask(const uint8_t *__restrict__ bits, uint8_t *__restrict__ mask, int64_t n) {
-    const int64_t nb = (n + 7) / 8;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t v = bits[i];
-        if (i * 8 + 8 <= n) {
-            uint64_t w = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) w |= (uint64_t)((v >> k) & 1u) << (8 * k);
-            memcpy(mask + i * 8, &w, 8);
-        } else {
-            for (int64_t k = 0; i * 8 + k < n; ++k) mask[i * 8 + k] = (uint8_t)((v >> k) & 1u);
-        }
-    }
-}
-
-static bool par_pack_mask(const uint8_t *src, uint8_t *dst, size_t n) {
-    const size_t chunk = (size_t)8 << 20;   // bytes of mask per task (a multiple of 8)
-    const int want = (int)std::max<size_t>(1, std::min<size_t>(VH_COPY_THREADS, (n + chunk - 1) / chunk));
-    std::vector<int> bad(want, 0);
-    auto run = [&](int t, size_t o, size_t m) {   // [o, o + m), o a multiple of 8
-        uint64_t hi = 0;
-        size_t i = o;
-        for (; i + 8 <= o + m; i += 8) {
-            uint64_t w;
-            memcpy(&w, src + i, 8);
-            hi |= w;
-            dst[i / 8] = (uint8_t)((w * 0x0102040810204080ull) >> 56);   // byte k's bit 0 -> bit k
-        }
-        if (i < o + m) {
-            uint8_t v = 0;
-            for (size_t k = 0; i + k < o + m; ++k) {
-                hi |= src[i + k];
-                v |= (uint8_t)((src[i + k] & 1u) << k);
-            }
-            dst[i / 8] = v;
-        }
-        bad[t] = (hi & 0xFEFEFEFEFEFEFEFEull) != 0;
-    };
-    const size_t per = ((n + want - 1) / want + 7) / 8 * 8;
-    std::vector<std::thread> th;
-    for (int t = 1; t < want; ++t) {
-        const size_t o = per * t;
-        if (o < n) th.emplace_back(run, t, o, std::min(per, n - o));
-    }
-    run(0, 0, std::min(per, n));
-    for (auto &x : th) x.join();
-    for (int t = 0; t < want; ++t)
-        if (bad[t]) return false;
-    return true;
-}
-
-// the caller's maps from the packed bytes (any of d / b / l may be null), on host threads
-static void par_unpack_maps(const uint8_t *src, uint8_t *d, uint8_t *b, uint8_t *l, size_t n) {
-    const size_t chunk = (size_t)8 << 20;
-    const int want = (int)std::min<size_t>(VH_COPY_THREADS, (n + chunk - 1) / chunk);
-    auto run = [=](size_t o, size_t m) {
-        for (size_t i = o; i < o + m; ++i) {
-            const uint8_t v = src[i];
-            if (d) d[i] = v & 1u;
-            if (b) b[i] = (v >> 1) & 1u;
-            if (l) l[i] = v >> 2;
-        }
-    };
-    if (want <= 1) {
-        run(0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t per = (n + want - 1) / want;
-    for (int i = 1; i < want; ++i) {
-        const size_t o = per * i;
-        if (o < n) th.emplace_back(run, o, std::min(per, n - o));
-    }
-    run(0, std::min(per, n));
-    for (auto &t : th) t.join();
-}
-
-static void par_memcpy(void *dst, const void *src, size_t bytes) {
-    const size_t chunk = (size_t)16 << 20;   // 16 MiB per task
-    const int want = (int)std::min<size_t>(VH_COPY_THREADS, (bytes + chunk - 1) / chunk);
-    if (want <= 1) {
-        memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t per = (bytes + want - 1) / want;
-    for (int i = 1; i < want; ++i) {
-        const size_t o = per * i, n = std::min(per, bytes - o);
-        th.emplace_back([=] { memcpy((char *)dst + o, (const char *)src + o, n); });
-    }
-    memcpy(dst, src, std::min(per, bytes));
-    for (auto &t : th) t.join();
-}
-
-// One host thread per slot; slot s owns batch b[s] (its own stream) and pinned staging, and takes
-// sub-batches s, s + slots, ...  Within a slot the steps are serial (stage in -> H2D -> pipeline ->
-// D2H -> stage out); across slots they overlap, so the copy engines, the host memcpys and the
-// compute of different sub-batches run at the same time.
-int vh_pipe_create(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t sub, int slots,
-                   vh_pipe **out) {
-    *out = nullptr;
-    API_TRY(ctx, {
-        if (sub < 1 || slots < 1 || slots > 8) throw VhError{VH_ERR_ARG, "pipe: sub >= 1, 1 <= slots <= 8"};
-        HIP_TRY(hipSetDevice(ctx->device));
-        vh_pipe *p = new vh_pipe;
-        p->ctx = ctx;
-        p->R = R; p->C = C; p->Z = Z; p->sub = sub;
-        // a per-node budget of 32 GiB page-locked, shared by the node's ranks (LOCAL_WORLD_SIZE, as
-        // torchrun and bench.py set it): 8 ranks pin at most 4 GiB each
-        int64_t local_ranks = 1;
-        if (const char *e = getenv("LOCAL_WORLD_SIZE")) local_ranks = std::max<int64_t>(1, atoll(e));
-        p->pin_cap = ((int64_t)32 << 30) / local_ranks;
-        if (const char *e = getenv("VH_PIPE_PIN_CAP")) p->pin_cap = atoll(e);
-        const size_t NV = (size_t)sub * R * C * Z;
-        try {
-            for (int s = 0; s < slots; ++s) {
-                p->slot.emplace_back();
-                vh_pipe::Slot &q = p->slot.back();
-                q.b = batch_new(ctx, R, C, Z, sub);
-                q.hp.reserve(NV);
-                q.n4.reserve(NV);
-                // the chunk's outputs leave the GPU as ONE copy: the per-study scalars and N4 states,
-                // then the packed maps.  Small copies (the scalars were two of ~20 / 11 KiB) run as
-                // blit kernels (__amd_rocclr_copyBuffer), which wait for a CU like any kernel -- for
-                // milliseconds while k_n4_study holds every CU's LDS (r4a trace); one large copy
-                // goes to the SDMA engines.
-                q.scal = (sizeof(VolScalars) * sub + sizeof(N4State) * sub + 4095) / 4096 * 4096;
-                q.u8.reserve(2 * NV + q.scal);   // mask in | scalars + maps out
-                HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&q.h2d, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&q.packed, hipEventDisableTiming));
-                q.d_pack.reserve((size_t)NV + q.scal);
-                q.mb_half = ((size_t)NV / 8 + 1 + 63) / 64 * 64;
-                q.mb.reserve(2 * q.mb_half);
-                q.sc = reinterpret_cast<VolScalars *>(q.u8 + NV);
-                q.st = reinterpret_cast<N4State *>(q.u8 + NV + sizeof(VolScalars) * sub);
-                q.res.resize(sub);
-            }
-        } catch (...) {
-            pipe_free(p);
-            throw;
-        }
-        *out = p;
-    })
-}
-
-// Host buffers the copy engines may read / write in place: hipHostRegister pins the caller's pages
-// (the page tables only; measured ~0.4-0.5 TB/s on the box, scripts/dev/h2h_probe.py) and the DMA
-// then runs at the link rate with no staging memcpy on a host thread.  A buffer that cannot be
-// registered (e.g. pages already registered, or VH_PIPE_STAGE=1) goes through the pinned staging.
-// First touch of a caller's output pages on several host threads (hipHostRegister would otherwise
-// fault in and zero every untouched page on the calling thread: measured 3.8k vs 5.1k vol/s staged)
-static void par_touch(void *dst, size_t bytes) {
-    const size_t page = 4096, chunk = (size_t)64 << 20;
-    const int want = (int)std::min<size_t>(2 * VH_COPY_THREADS, (bytes + chunk - 1) / chunk);
-    auto touch = [=](size_t o, size_t n) {
-        volatile char *q = (volatile char *)dst + o;
-        for (size_t i = 0; i < n; i += page) q[i] = q[i];
-    };
-    if (want <= 1) {
-        touch(0, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t per = ((bytes + want - 1) / want + page - 1) / page * page;
-    for (int i = 1; i < want; ++i) {
-        const size_t o = per * i;
-        if (o < bytes) th.emplace_back(touch, o, std::min(per, bytes - o));
-    }
-    touch(0, std::min(per, bytes));
-    for (auto &t : th) t.join();
-}
-
-struct HostPin {
-    void *p = nullptr;
-    size_t n = 0;
-    vh_pipe *owner = nullptr;   // the pipe whose pin budget this registration counts against
-    HostPin() = default;
-    HostPin(const HostPin &) = delete;
-    HostPin &operator=(const HostPin &) = delete;
-    bool pin(const void *ptr, size_t bytes, bool touch, vh_pipe *pp) {
-        if (!ptr || !bytes || getenv("VH_PIPE_STAGE")) return false;
-        // the budget first: a run over more than pin_cap bytes of caller memory stages the rest
-        // rather than page-locking all of it (counted in staged_spans, vh_pipe_stats)
-        const int64_t now = pp->pinned.fetch_add((int64_t)bytes) + (int64_t)bytes;
-        if (now > pp->pin_cap) {
-            pp->pinned.fetch_sub((int64_t)bytes);
-            return false;
-        }
-        int64_t pk = pp->pinned_peak.load();
-        while (now > pk && !pp->pinned_peak.compare_exchange_weak(pk, now)) {
-        }
-        if (touch) par_touch(const_cast<void *>(ptr), bytes);
-        if (hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            pp->pinned.fetch_sub((int64_t)bytes);
-            return false;
-        }
-        p = const_cast<void *>(ptr);
-        n = bytes;
-        owner = pp;
-        return true;
-    }
-    ~HostPin() {
-        if (p) {
-            (void)hipHostUnregister(p);
-            owner->pinned.fetch_sub((int64_t)n);
-        }
-    }
-};
-
-struct PipeAbort {   // a pipe slot stopped because another slot failed
-    int slot = -1;
-};
-
-// One caller range of a pipe chunk.  Only its whole pages are pinned (and DMA'd in place): a page
-// it shares with the neighbouring chunk or another buffer must never be registered twice or
-// unregistered under another range's copy, so the head and tail fragments (< 1 page each) go
-// through the slot's pinned staging at the same offsets.  A range that cannot be pinned is staged.
-struct PipeSpan {
-    char *p = nullptr;
-    size_t n = 0, h = 0, t = 0;
-    bool direct = false;
-    HostPin pin;
-    void plan(const void *ptr, size_t bytes, bool touch, vh_pipe *pp) {
-        p = (char *)ptr;
-        n = ptr ? bytes : 0;
-        if (!n) return;
-        const uintptr_t pg = 4096, s0 = (uintptr_t)p, e0 = s0 + n;
-        const uintptr_t a = (s0 + pg - 1) / pg * pg, e = e0 / pg * pg;
-        if (e <= a || e - a < ((size_t)1 << 20)) return;   // small: staged
-        if (!pin.pin((void *)a, e - a, touch, pp)) {
-            pp->staged_spans.fetch_add(1);
-            return;
-        }
-        h = a - s0;
-        t = e0 - e;
-        direct = true;
-    }
-    void h2d(char *dst, char *stage, hipStream_t st) {
-        if (!n) return;
-        if (!direct) {
-            par_memcpy(stage, p, n);
-            HIP_TRY(hipMemcpyAsync(dst, stage, n, hipMemcpyHostToDevice, st));
-            return;
-        }
-        if (h) {
-            memcpy(stage, p, h);
-            HIP_TRY(hipMemcpyAsync(dst, stage, h, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipMemcpyAsync(dst + h, p + h, n - h - t, hipMemcpyHostToDevice, st));
-        if (t) {
-            memcpy(stage + n - t, p + n - t, t);
-            HIP_TRY(hipMemcpyAsync(dst + n - t, stage + n - t, t, hipMemcpyHostToDevice, st));
-        }
-    }
-    void d2h(const char *src, char *stage, hipStream_t st) {
-        if (!n) return;
-        if (!direct) {
-            HIP_TRY(hipMemcpyAsync(stage, src, n, hipMemcpyDeviceToHost, st));
-            return;
-        }
-        if (h) HIP_TRY(hipMemcpyAsync(stage, src, h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(p + h, src + h, n - h - t, hipMemcpyDeviceToHost, st));
-        if (t) HIP_TRY(hipMemcpyAsync(stage + n - t, src + n - t, t, hipMemcpyDeviceToHost, st));
-    }
-    void d2h_finish(const char *stage) {   // after the stream sync
-        if (!n) return;
-        if (!direct) {
-            par_memcpy(p, stage, n);
-            return;
-        }
-        if (h) memcpy(p, stage, h);
-        if (t) memcpy(p + n - t, stage + n - t, t);
-    }
-};
-
-int vh_pipe_run(vh_pipe *p, const float *hp, const uint8_t *mask, int64_t n, const vh_run_opts *opts,
-                float *n4, uint8_t *defect, uint8_t *defect_border, uint8_t *lb, vh_vdp_result *res) {
-    API_TRY(p->ctx, {
-        if (!opts || !hp || !mask || n < 1) throw VhError{VH_ERR_ARG, "pipe: null input or n < 1"};
-        const int64_t V = p->R * p->C * p->Z, sub = p->sub;
-        const int64_t nchunk = (n + sub - 1) / sub;
-        const int slots = (int)p->slot.size();
-        HIP_TRY(hipSetDevice(p->ctx->device));
-        std::vector<VhError> err(slots);
-        std::vector<int> failed(slots, 0);
-        // VH_PIPE_TRACE=1: per chunk, host times (ms from the start) of the input pin + H2D enqueue, the
-        // pipeline enqueue, the output pin, the sync, and device times of H2D / compute / D2H ends (stderr)
-        struct Mark {
-            int64_t k;
-            double h[5];
-            hipEvent_t e[3];
-        };
-        const bool trace = getenv("VH_PIPE_TRACE") != nullptr;
-        p->pinned_peak = 0;
-        p->staged_spans = 0;
-        std::vector<std::vector<std::unique_ptr<PipeSpan[]>>> keep(slots);
-        std::vector<std::vector<Mark>> marks(slots);
-        hipEvent_t ev0 = nullptr;
-        const auto c0 = std::chrono::steady_clock::now();
-        auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count(); };
-        if (trace) {
-            HIP_TRY(hipEventCreate(&ev0));
-            HIP_TRY(hipEventRecord(ev0, p->slot[0].b->stream));
-        }
-        auto mark_ev = [&](Mark &m, int i, hipStream_t st) {
-            if (trace && hipEventCreate(&m.e[i]) == hipSuccess) (void)hipEventRecord(m.e[i], st);
-        };
-        // Chunk k's pipeline waits on the device for chunk k - lag's (lag = the chunks that fill the
-        // CUs, VH_PIPE_LAG overrides; 0 = no ordering).  Without it the slots ran in lockstep: all
-        // computing together, then all copying out / in together with the GPU idle (~60% of the
-        // device rate, VH_PIPE_TRACE); with it the computes are staggered and each chunk's copies
-        // overlap the next chunks' compute.  Enqueues happen in chunk order (host-side ticket).
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device);
-        int lag = (int)std::max<int64_t>(1, (cus + sub - 1) / sub);
-        if (const char *e = getenv("VH_PIPE_LAG")) lag = atoi(e);
-        lag = std::min(lag, slots);
-        std::mutex tk_mu;
-        std::condition_variable tk_cv;
-        int64_t tk_next = 0;   // the chunk whose pipeline is enqueued next
-        bool tk_abort = false;
-        auto ticket_wait = [&](int64_t k) {
-            std::unique_lock<std::mutex> lk(tk_mu);
-            tk_cv.wait(lk, [&] { return tk_next == k || tk_abort; });
-            if (tk_abort && tk_next != k) throw PipeAbort{};
-        };
-        auto ticket_pass = [&](int64_t k) {
-            {
-                std::lock_guard<std::mutex> lk(tk_mu);
-                if (tk_next == k) tk_next = k + 1;
-            }
-            tk_cv.notify_all();
-        };
-        auto ticket_abort = [&] {
-            {
-                std::lock_guard<std::mutex> lk(tk_mu);
-                tk_abort = true;
-            }
-            tk_cv.notify_all();
-        };
-        // Per slot, chunk by chunk: prep (host: pin the input pages, pack the mask bits) -> front
-        // (enqueue H2D, the pipeline behind its ticket and lag event, the map packing) -> back
-        // (first-touch + pin the n4 output pages, enqueue the D2Hs) -> sync -> finish (results,
-        // fragments, map unpacking).  The next chunk's prep runs before this chunk's sync and its
-        // front right after it, so the host work of finish overlaps the next chunk's H2D and
-        // compute (its D2H is enqueued after finish: the staging it writes is free by then).
-        struct Chunk {
-            int64_t k = -1, v0 = 0, cnt = 0;
-            size_t CV = 0;
-            PipeSpan *sp = nullptr;
-            bool mbits = false;
-            uint8_t *mb = nullptr;
-            Mark mk{};
-        };
-        const bool maps = defect || defect_border || lb;
-        // A/B switches (VH_PIPE_H2D_ORDER, VH_PIPE_D2H_LATE: 0 / 1) for the copy ordering below
-        auto env_flag = [](const char *name, bool dflt) {
-            const char *e = getenv(name);
-            return e ? atoi(e) != 0 : dflt;
-        };
-        // H2D order: 0 none, 1 device-side (the H2D waits on the previous chunk's H2D event),
-        // 2 host-side (the enqueuing thread waits for that event first)
-        const char *ho = getenv("VH_PIPE_H2D_ORDER");
-        const int h2d_order = ho ? atoi(ho) : 2;
-        // No copy is enqueued before what it depends on has finished (host-side waits): a copy
-        // enqueued behind unfinished work waits on the DMA engine's queue and holds back every
-        // later copy of that engine -- an H2D stuck behind another chunk's D2H that waits for a
-        // kernel which waits for a CU (r4b trace: 30 ms stalls).  The D2H waits for the chunk's
-        // packing kernel (not just the pipeline: the packing may itself wait for a free CU).
-        const bool d2h_late = env_flag("VH_PIPE_D2H_LATE", true);
-        auto work = [&](int s) {
-            vh_pipe::Slot &q = p->slot[s];
-            vh_batch *b = q.b;
-            // mask bytes in (fallback); the D2H block: scalars / states, then the packed maps
-            uint8_t *qm = q.u8, *qd = q.u8 + sub * V + q.scal;
-            auto prep = [&](Chunk &c, int64_t k) {
-                c.k = k;
-                c.v0 = k * sub;
-                c.cnt = std::min(sub, n - c.v0);
-                c.CV = (size_t)c.cnt * V;
-                c.mk = Mark{k, {now_ms(), 0, 0, 0, 0}, {nullptr, nullptr, nullptr}};
-                // the spans' pins are released only after the whole run (hipHostUnregister waits
-                // for the device: released per chunk, it lined every slot up behind the others)
-                keep[s].emplace_back(new PipeSpan[3]);
-                c.sp = keep[s].back().get();
-                c.sp[0].plan(hp + c.v0 * V, sizeof(float) * c.CV, false, p);
-                c.mb = q.mb + ((k / slots) & 1) * q.mb_half;   // bits double-buffered across chunks
-                c.mbits = !getenv("VH_PIPE_STAGE") && par_pack_mask(mask + c.v0 * V, c.mb, c.CV);
-                if (!c.mbits) c.sp[1].plan(mask + c.v0 * V, c.CV, false, p);
-            };
-            auto front = [&](Chunk &c) {
-                const size_t CV = c.CV;
-                // enqueues in chunk order; the H2Ds also run in chunk order (each waits for the one
-                // before): at the start the first chunks' inputs get the whole link instead of
-                // every slot's sharing it
-                ticket_wait(c.k);
-                try {
-                if (h2d_order == 1 && c.k > 0)
-                    HIP_TRY(hipStreamWaitEvent(b->stream, p->slot[(c.k - 1) % slots].h2d, 0));
-                if (h2d_order == 2 && c.k > 0) HIP_TRY(hipEventSynchronize(p->slot[(c.k - 1) % slots].h2d));
-                // the copies first (the event marks their end: the next chunk's H2D waits for it
-                // on the host), then the kernels that consume them
-                c.sp[0].h2d((char *)b->d_hp.get(), (char *)q.hp.get(), b->stream);
-                if (c.mbits) HIP_TRY(hipMemcpyAsync(q.d_pack, c.mb, (CV + 7) / 8, hipMemcpyHostToDevice, b->stream));
-                else c.sp[1].h2d((char *)b->d_mask.get(), (char *)qm, b->stream);
-                HIP_TRY(hipEventRecord(q.h2d, b->stream));
-                if (c.mbits) {
-                    k_unpack_mask<<<(unsigned)std::min<int64_t>(4096, ((int64_t)(CV + 7) / 8 + 255) / 256), 256, 0,
-                                    b->stream>>>(q.d_pack, b->d_mask, (int64_t)CV);
-                    HIP_TRY(hipGetLastError());
-                }
-                if (c.cnt < sub) {   // ragged tail: repeat the last study (a kernel, not DMA copies)
-                    k_repeat_last<<<(unsigned)std::min<int64_t>(4096, (sub - c.cnt) * (V / 4 + 255) / 256 + 1), 256, 0,
-                                    b->stream>>>(b->d_hp, b->d_mask, V, c.cnt, sub);
-                    HIP_TRY(hipGetLastError());
-                }
-                mark_ev(c.mk, 0, b->stream);
-                c.mk.h[1] = now_ms();
-                if (lag > 0 && c.k >= lag)
-                    HIP_TRY(hipStreamWaitEvent(b->stream, p->slot[(c.k - lag) % slots].done, 0));
-                batch_run(b, *opts, opts->do_n4 ? 0 : 1);
-                HIP_TRY(hipEventRecord(q.done, b->stream));
-                } catch (...) {
-                    ticket_pass(c.k);
-                    throw;
-                }
-                ticket_pass(c.k);
-                mark_ev(c.mk, 1, b->stream);
-                c.mk.h[2] = now_ms();
-                if (maps || res) {   // scalars + the three maps packed into one byte per voxel
-                    const int64_t cvm = maps ? (int64_t)CV : 0;
-                    const int64_t scw = (int64_t)(sizeof(VolScalars) * sub / 4);
-                    const int64_t stw = opts->do_n4 ? (int64_t)(sizeof(N4State) * sub / 4) : 0;
-                    k_pack_maps<<<(unsigned)std::min<int64_t>(4096, (cvm / 16 + 255) / 256 + 1), 256, 0,
-                                  b->stream>>>(b->d_defect, b->d_border, b->d_lb, q.d_pack + q.scal, cvm,
-                                               reinterpret_cast<const uint32_t *>(b->d_sc.get()), scw,
-                                               reinterpret_cast<const uint32_t *>(b->d_st.get()), stw,
-                                               reinterpret_cast<uint32_t *>(q.d_pack.get()));
-                    HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(q.packed, b->stream));
-            };
-            auto back_pin = [&](Chunk &c) {   // while the chunk computes: first touch + pin of its output pages
-                c.sp[2].plan(n4 ? n4 + c.v0 * V : nullptr, sizeof(float) * c.CV, true, p);
-            };
-            auto back = [&](Chunk &c) {
-                const float *dn4 = opts->do_n4 ? b->d_n4 : b->d_hp;
-                c.sp[2].d2h((const char *)dn4, (char *)q.n4.get(), b->stream);
-                if (maps || res)   // one D2H: the scalars / states block, then the packed maps
-                    HIP_TRY(hipMemcpyAsync(q.u8 + sub * V, q.d_pack, q.scal + (maps ? c.CV : 0),
-                                           hipMemcpyDeviceToHost, b->stream));
-                mark_ev(c.mk, 2, b->stream);
-                c.mk.h[3] = now_ms();
-            };
-            auto finish = [&](Chunk &c) {
-                if (res) {
-                    fill_results_from(b, q.sc, q.st, q.res.data());
-                    memcpy(res + c.v0, q.res.data(), sizeof(vh_vdp_result) * c.cnt);
-                }
-                c.sp[2].d2h_finish((const char *)q.n4.get());
-                if (maps)
-                    par_unpack_maps(qd, defect ? defect + c.v0 * V : nullptr,
-                                    defect_border ? defect_border + c.v0 * V : nullptr,
-                                    lb ? lb + c.v0 * V : nullptr, c.CV);
-                if (trace) marks[s].push_back(c.mk);
-            };
-            try {
-                HIP_TRY(hipSetDevice(p->ctx->device));
-                Chunk cur, nxt;
-                if (s < nchunk) {
-                    try {
-                        prep(cur, s);
-                        front(cur);
-                        for (;;) {
-                            const int64_t kn = cur.k + slots;
-                            if (kn < nchunk) prep(nxt, kn);   // host work while the GPU has cur
-                            back_pin(cur);
-                            // VH_PIPE_D2H_LATE=1 enqueues the D2Hs only once the compute has
-                            // finished (A/B: neutral to -2 % on the boxes measured, r3q3; off)
-                            if (d2h_late) HIP_TRY(hipEventSynchronize(q.packed));
-                            back(cur);
-                            HIP_TRY(hipStreamSynchronize(b->stream));
-                            cur.mk.h[4] = now_ms();
-                            if (kn < nchunk) front(nxt);      // the next chunk's H2D + compute first
-                            finish(cur);                      // then this chunk's host side
-                            if (kn >= nchunk) break;
-                            cur = nxt;
-                        }
-                    } catch (...) {   // no copy may still touch a pinned range when it is released
-                        (void)hipStreamSynchronize(b->stream);
-                        throw;
-                    }
-                }
-            } catch (const PipeAbort &) {   // another slot's failure is the one reported
-                failed[s] = 2;
-            } catch (const VhError &e) {
-                err[s] = e;
-                failed[s] = 1;
-                ticket_abort();
-            } catch (const std::exception &e) {
-                err[s] = VhError{VH_ERR_HIP, e.what()};
-                failed[s] = 1;
-                ticket_abort();
-            }
-        };
-        std::vector<std::thread> th;
-        for (int s = 1; s < slots; ++s) th.emplace_back(work, s);
-        work(0);
-        for (auto &t : th) t.join();
-        for (int s = 0; s < slots; ++s)   // no copy may still touch a pinned buffer when it is released
-            (void)hipStreamSynchronize(p->slot[s].b->stream);
-        keep.clear();
-        if (trace) {
-            fprintf(stderr, "pipe_trace total_ms %.2f\n", now_ms());
-            for (int s = 0; s < slots; ++s)
-                for (Mark &m : marks[s]) {
-                    float d[3] = {-1, -1, -1};
-                    for (int i = 0; i < 3; ++i)
-                        if (m.e[i]) {
-                            (void)hipEventElapsedTime(&d[i], ev0, m.e[i]);
-                            (void)hipEventDestroy(m.e[i]);
-                        }
-                    fprintf(stderr, "pipe_trace slot %d chunk %lld host %.2f %.2f %.2f %.2f %.2f dev %.2f %.2f %.2f\n", s,
-                            (long long)m.k, m.h[0], m.h[1], m.h[2], m.h[3], m.h[4], d[0], d[1], d[2]);
-                }
-            (void)hipEventDestroy(ev0);
-        }
-        for (int s = 0; s < slots; ++s)
-            if (failed[s] == 1) throw err[s];
-    })
-}
-
-int vh_pipe_stats(vh_pipe *p, int64_t *pinned_peak_bytes, int64_t *staged_spans) {
-    if (!p) return VH_ERR_ARG;
-    if (pinned_peak_bytes) *pinned_peak_bytes = p->pinned_peak.load();
-    if (staged_spans) *staged_spans = p->staged_spans.load();
-    return VH_OK;
-}
-
 int vh_link_probe(vh_ctx *ctx, int64_t bytes, double out_gbps[3]) {
     API_TRY(ctx, {
         std::lock_guard<std::mutex> lock(ctx->mu);
@@ -2422,14 +1793,6 @@ int vh_host_free(void *p) {
             g_host.erase((uintptr_t)p);
         }
         (void)hipHostFree(p);
-    }
-    return VH_OK;
-}
-
-int vh_pipe_destroy(vh_pipe *p) {
-    if (p) {
-        (void)hipSetDevice(p->ctx->device);
-        pipe_free(p);
     }
     return VH_OK;
 }

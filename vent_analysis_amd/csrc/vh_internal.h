@@ -4,12 +4,10 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <atomic>
 #include <map>
+#include <new>
 #include <set>
-#include <condition_variable>
 #include <mutex>
-#include <thread>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -158,31 +156,6 @@ struct vh_ctx {
     // order than another rank does: a deadlock)
     hipStream_t comm_st = nullptr;
     Buf<char> recon_buf;
-};
-
-struct vh_pipe {
-    struct Slot {
-        vh_batch *b = nullptr;
-        Buf<float, 1> hp, n4;                 // pinned staging [sub][V]
-        Buf<uint8_t, 1> u8;                   // pinned: mask in [sub][V], then the D2H block (scal + [sub][V])
-        hipEvent_t done = nullptr;            // recorded after the slot's current chunk's pipeline
-        hipEvent_t h2d = nullptr;             // recorded after the slot's current chunk's H2D
-        hipEvent_t packed = nullptr;          // recorded after the chunk's output packing (its D2H may start)
-        Buf<uint8_t> d_pack;                  // device: the chunk's D2H block: scalars (scal bytes), packed maps
-        size_t scal = 0;                      // bytes of the per-study scalars + N4 states block (4 KiB multiple)
-        Buf<uint8_t, 1> mb;                   // pinned: mask bits, two chunks' worth (double buffer)
-        size_t mb_half = 0;
-        VolScalars *sc = nullptr;             // the chunk's per-study scalars / N4 states: views into u8
-        N4State *st = nullptr;
-        std::vector<vh_vdp_result> res;
-    };
-    vh_ctx *ctx = nullptr;
-    int64_t R = 0, C = 0, Z = 0, sub = 0;
-    std::vector<Slot> slot;
-    // caller pages pinned in place during a run (released at its end), capped at pin_cap bytes
-    // (VH_PIPE_PIN_CAP, default 32 GiB): past the cap a range goes through the pinned staging
-    int64_t pin_cap = 0;
-    std::atomic<int64_t> pinned{0}, pinned_peak{0}, staged_spans{0};
 };
 
 // One study of the batch montage (vh_batch_montage_layout): its crop, how its crop rows split into
@@ -349,6 +322,38 @@ struct vh_batch {
         return state.n4_source() == N4Source::n4 ? d_n4.get() : d_hp.get();
     }
 };
+
+// ---- the extern "C" boundary (api.hip, pipe.hip) ----------------------------------------------
+int vh_fail(vh_ctx *c, int code, const std::string &msg);
+
+#define API_TRY(ctx, ...)                                                                    \
+    try {                                                                                    \
+        __VA_ARGS__                                                                          \
+    } catch (const VhError &e) {                                                             \
+        return vh_fail(ctx, e.code, e.msg);                                                  \
+    } catch (const std::bad_alloc &) {                                                       \
+        return vh_fail(ctx, VH_ERR_NOMEM, "host allocation failed");                         \
+    } catch (const std::exception &e) {                                                      \
+        return vh_fail(ctx, VH_ERR_HIP, e.what());                                           \
+    } catch (...) {                                                                          \
+        return vh_fail(ctx, VH_ERR_HIP, "unknown error");                                    \
+    }                                                                                        \
+    return VH_OK;
+
+// Every vh_batch_* entry point but vh_batch_destroy: a null handle is VH_ERR_ARG; otherwise API_TRY on
+// the batch's context, with its device current.
+#define BATCH_TRY(b, ...)                                                                    \
+    if (!(b)) return VH_ERR_ARG;                                                             \
+    API_TRY((b)->ctx, {                                                                      \
+        HIP_TRY(hipSetDevice((b)->ctx->device));                                             \
+        __VA_ARGS__                                                                          \
+    })
+
+// batches as api.hip makes, frees (after draining their stream) and runs them, for the pipe's slots
+vh_batch *vh_new_batch(vh_ctx *ctx, int64_t R, int64_t C, int64_t Z, int64_t nb);
+void vh_free_batch(vh_batch *b);
+void vh_run_batch(vh_batch *b, const vh_run_opts &o, int n4_src);
+void vh_fill_results(const vh_batch *b, const VolScalars *sc, const N4State *st, vh_vdp_result *res);
 
 // a compact sphere table resident in HBM (vh_ci_table_create): linear offsets for one (R, C)
 struct vh_ci_table {
