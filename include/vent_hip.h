@@ -56,6 +56,11 @@
  *                slice that its border does not reach, and an opening, specified to the byte; and the
  *                overlap counts against another mask (build-defined); kernel-timing class "segment_b",
  *                not listed
+ *   vh_batch_upload_proton_src / vh_batch_resample_proton / vh_batch_download_proton_src /
+ *   vh_resample_taps / vh_resample
+ *                a proton on its own grid (another matrix, pixel size or slice spacing) resampled onto the
+ *                batch's by a separable anti-aliased linear filter, specified to the last bit
+ *                (build-defined); kernel-timing class "resample_b", not listed
  *   vh_pipe_*   the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -611,8 +616,9 @@ int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z
  * for the code pass, "segment_max_b" for the two maximum sweeps and "shift_b" (vh_batch_kernel_time reads
  * them; vh_batch_kernel_names does not list them).
  *
- * Not done here: sub-voxel shifts, rotation, scaling, deformable registration, and protons on a
- * different grid from the xenon (vh_batch_upload_proton takes the batch's shape only). */
+ * Not done here: a search over sub-voxel shifts, rotation, scaling, deformable registration.  (A proton
+ * on another grid than the xenon's comes in through the resampling section below, which also applies a
+ * sub-voxel offset.) */
 #define VH_SHIFT_PROTON 0
 #define VH_SHIFT_MASK 1
 int vh_batch_register(vh_batch *b, const int32_t search[3], double *score /* [nb][ns] */, int32_t *best /* [nb][3] */,
@@ -624,6 +630,74 @@ int vh_batch_shift(vh_batch *b, int what, const int32_t *shift /* [nb][3] */);
 int vh_batch_download_proton(vh_batch *b, float *proton /* [nb][V] */);
 int vh_register(vh_ctx *ctx, const float *proton, const float *hp, int64_t R, int64_t C, int64_t Z, int64_t batch,
                 const int32_t search[3], double *score, int32_t *best, int32_t *status, float *shifted_out);
+
+/* ---- the proton resampled from its own grid onto the xenon grid of a batch ---------------------------
+ * A proton series is rarely on the xenon's grid: a 256 x 256 matrix at half the pixel size, or another
+ * slice spacing, is ordinary.  The source proton is staged on the device on its own grid and resampled
+ * into the batch's proton buffer by a separable, anti-aliased linear filter whose tap tables are made on
+ * the host in double; every device operation is a separately rounded float32 multiply or add in a fixed
+ * order (no fused multiply-add), so the result is specified to the last bit (tests/resample_ref.py is the
+ * same arithmetic in numpy).  The source stays resident, so it can be resampled again with a refined map
+ * (a registration's best shift folded into the offsets) instead of being shifted with zeros pulled in.
+ *
+ * Volumes.  The source S is float32 [nb][Rs][Cs][Zs], the slice axis fastest; one source shape holds for
+ * the whole batch, 1 <= Rs, Cs, Zs <= 1024.  The destination is the batch's [nb][R][C][Z] and lands in the
+ * resident proton.
+ *
+ * Map.  Per study and per axis a (r, c, z) two doubles (scale_a, offset_a): map is double [nb][3][2].
+ * Destination index i looks at source coordinate u = scale * (double)i + offset: one multiply and one
+ * add in double, not contracted.  Coordinates are in source voxel-index units, voxel centres at the
+ * integers.  Limits: scale finite in [0.25, 4], offset finite with |offset| <= 2^20.
+ *
+ * Taps of one axis (vh_resample_taps, a host function: no context, no device), n_src 1..1024, n_dst
+ * 1..2^20.  With w = max(1.0, scale): for integer j, t_j = 1.0 - fabs((double)j - u) / w, in that
+ * operation order in double.  The taps are every j with t_j > 0: at most VH_RESAMPLE_TAPS = 8, since they
+ * lie in an open interval of length 2 w <= 8.  W is the sum of the t_j in ascending j, starting from 0.0;
+ * weight_j = (float)(t_j / W).  Taps with j outside [0, n_src) are dropped after the normalisation, so
+ * outside the source counts as zeros, like vh_batch_shift.  The result per destination index is first
+ * (the lowest in-range j; 0 when there is none), count (0..8; the in-range taps are contiguous) and
+ * weight[8] (the in-range weights from slot 0, the rest 0.0f).
+ *
+ * Value of destination voxel (r, c, z), with the three tables of its study:
+ *   ar = +0.0f
+ *   for the r taps, ascending:
+ *       ac = +0.0f
+ *       for the c taps, ascending:
+ *           az = +0.0f
+ *           for the z taps, ascending:   az = az + wz * S[jr][jc][jz]
+ *           ac = ac + wc * az
+ *       ar = ar + wr * ac
+ *   out = ar
+ * Every multiply and every add is rounded to float32 on its own.  An axis with count 0 gives +0.0f.
+ * Non-finite voxels follow the same pointwise rules.  The nested form is exactly separable -- the z-sum
+ * depends on (jr, jc, z) only and the c-sum on (jr, c, z) only -- so staging the passes changes no bit.
+ * Under the identity map (1, 0) every axis has one tap of weight 1.0f and out = +0.0f + 1.0f * S: the
+ * source, with -0.0 become +0.0.
+ *
+ * vh_batch_upload_proton_src stages the source in a device buffer of its own (allocated or grown on
+ * first use: nb * Rs * Cs * Zs * 4 bytes), returns once the caller's buffer is free, and invalidates
+ * nothing.  vh_batch_resample_proton builds the nb x 3 tables on the host, uploads them and enqueues the
+ * resampling of the resident source into the resident proton; it marks the proton resident exactly as
+ * vh_batch_upload_proton does and invalidates nothing else; map may be reused on return.
+ * vh_batch_download_proton_src waits and returns the resident source.  vh_resample is the host-buffer
+ * form on the context's scratch batch.
+ *
+ * VH_ERR_ARG, with nothing enqueued or changed: a null batch or a null required pointer, a source shape
+ * outside the limits, a map outside the limits or not finite, vh_batch_resample_proton or
+ * vh_batch_download_proton_src without a resident source (and a batch of more than 65535 studies, or
+ * with a dimension above 2^20, the largest n_dst a tap table is made for).  Every other batch shape is
+ * taken.  An upload that fails leaves no source resident.  The kernel-timing class is "resample_b"
+ * (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * Not done here: rotation, non-diagonal maps (shear, axis exchange), masks resampled from another grid. */
+#define VH_RESAMPLE_TAPS 8
+int vh_resample_taps(int64_t n_src, int64_t n_dst, double scale, double offset, int32_t *first /* [n_dst] */,
+                     int32_t *count /* [n_dst] */, float *weight /* [n_dst][8] */);
+int vh_batch_upload_proton_src(vh_batch *b, const float *src /* [nb][Rs][Cs][Zs] */, const int64_t shape[3]);
+int vh_batch_resample_proton(vh_batch *b, const double *map /* [nb][3][2] */);
+int vh_batch_download_proton_src(vh_batch *b, float *src);
+int vh_resample(vh_ctx *ctx, const float *src, const int64_t src_shape[3], int64_t R, int64_t C, int64_t Z,
+                int64_t batch, const double *map, float *out /* [batch][R][C][Z] */);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

@@ -385,6 +385,32 @@ class Vent_Analysis:
             self.proton = out
         return (dr, dc, dz), value
 
+    def resample_proton(self, proton_vox=None, shift=(0, 0, 0)):
+        """Resample ``self.proton`` from its own grid onto HPvent's (build-defined), on the GPU: a
+        separable, anti-aliased linear filter specified to the last bit in include/vent_hip.h, with the
+        two fields of view centre on centre (_lib.grid_map).  ``self.proton`` may have any 3-D shape with
+        dimensions of 1..1024; ``proton_vox`` is its voxel size [dx, dy, dz] in the units of ``self.vox``
+        and defaults to the proton DICOM header's when there is one; ``shift`` (dr, dc, dz), in HPvent's
+        voxels, moves the result as register_proton's shift does, with the proton's own data in the margin
+        instead of zeros.  ``self.proton`` becomes the resampled float32 array of HPvent's shape, which is
+        returned; nothing else is changed.  register_proton and segment_mask work after it."""
+        p = self.proton
+        if isinstance(p, str) or np.ndim(p) != 3:
+            raise ValueError("resample_proton: self.proton must be a 3-D array")
+        if np.ndim(self.HPvent) != 3:
+            raise ValueError("resample_proton: self.HPvent must be a 3-D array")
+        if isinstance(self.vox, str):
+            raise ValueError("resample_proton: self.vox is not set")
+        if proton_vox is None:
+            ds = getattr(self, 'proton_ds', None)
+            if ds is None or isinstance(ds, str):
+                raise ValueError("resample_proton: pass proton_vox (there is no proton DICOM header to read it from)")
+            proton_vox = ingest.header_vox(ds)
+        m = _lib.grid_map(np.shape(p), proton_vox, np.shape(self.HPvent), self.vox, shift)
+        _lib._resample_args(m, 1, np.shape(p))
+        self.proton = _lib.resample(np.asarray(p, dtype=np.float32), np.shape(self.HPvent), m, device=self.device)[0]
+        return self.proton
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

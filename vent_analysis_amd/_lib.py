@@ -210,6 +210,83 @@ def _score_shape(search):
     return (2 * int(search[2]) + 1, 2 * int(search[0]) + 1, 2 * int(search[1]) + 1)
 
 
+RESAMPLE_TAPS = 8                           # VH_RESAMPLE_TAPS: taps of one axis at most
+RESAMPLE_MAX_SRC = 1024                     # the largest source dimension
+RESAMPLE_SCALE = (0.25, 4.0)                # the limits of a map's scale
+RESAMPLE_MAX_OFFSET = float(1 << 20)        # ... and of |offset|
+
+
+def _real_array(a, what):
+    x = np.asarray(a)
+    if x.dtype == np.bool_ or not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.integer)):
+        raise ValueError(f"{what}: numbers, got {a!r}")
+    return x.astype(np.float64)
+
+
+def _shape3(shape, what, hi=None):
+    s = np.asarray(shape)
+    if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer) or s.shape != (3,):
+        raise ValueError(f"{what} is three ints, got {shape!r}")
+    if (s < 1).any() or (hi is not None and (s > hi).any()):
+        raise ValueError(f"{what}: every dimension must be 1..{hi if hi is not None else ''}, got {shape!r}")
+    return tuple(int(v) for v in s)
+
+
+def resample_taps(n_src, n_dst, scale, offset):
+    """The tap table of one axis of the resampler (vh_resample_taps, on the host: no device; the spec is in
+    include/vent_hip.h): destination index i looks at source coordinate scale * i + offset.  Returns
+    (first int32 [n_dst], count int32 [n_dst], weight float32 [n_dst][8])."""
+    n_src, n_dst = int(n_src), int(n_dst)
+    if n_dst < 1:
+        raise ValueError(f"resample_taps: n_dst must be >= 1, got {n_dst}")
+    first, count = np.zeros(n_dst, np.int32), np.zeros(n_dst, np.int32)
+    weight = np.zeros((n_dst, RESAMPLE_TAPS), np.float32)
+    rc = lib().vh_resample_taps(n_src, n_dst, float(scale), float(offset), _ptr(first), _ptr(count), _ptr(weight))
+    if rc != VH_OK:
+        raise ValueError(f"resample_taps: n_src 1..{RESAMPLE_MAX_SRC}, scale in {list(RESAMPLE_SCALE)}, |offset| <= 2^20, "
+                         f"got n_src {n_src}, n_dst {n_dst}, scale {scale!r}, offset {offset!r}")
+    return first, count, weight
+
+
+def grid_map(src_shape, src_vox, dst_shape, dst_vox, shift=(0, 0, 0)):
+    """The map float64 [3][2] of (scale, offset) per axis that puts the fields of view of two grids centre
+    on centre: scale = dst_vox / src_vox and offset = (n_src - 1) / 2 - scale * (n_dst - 1) / 2 + scale * shift.
+    ``shift`` is in destination voxels, so a registration's best shift can be folded into the map: the
+    result is the unshifted resampling moved as vh_batch_shift moves it, with the source's own data in the
+    margin instead of zeros."""
+    ns = np.asarray(_shape3(src_shape, "grid_map: src_shape"), np.float64)
+    nd = np.asarray(_shape3(dst_shape, "grid_map: dst_shape"), np.float64)
+    vs, vd, sh = (_real_array(v, "grid_map: " + k) for v, k in ((src_vox, "src_vox"), (dst_vox, "dst_vox"),
+                                                                (shift, "shift")))
+    if vs.shape != (3,) or vd.shape != (3,) or sh.shape != (3,):
+        raise ValueError("grid_map: src_vox, dst_vox and shift have three values each")
+    if not (np.isfinite(vs).all() and np.isfinite(vd).all() and (vs > 0).all() and (vd > 0).all()):
+        raise ValueError(f"grid_map: voxel sizes must be finite and > 0, got {src_vox!r} and {dst_vox!r}")
+    scale = vd / vs
+    offset = (ns - 1.0) / 2.0 - scale * (nd - 1.0) / 2.0 + scale * sh
+    return np.ascontiguousarray(np.stack([scale, offset], axis=1))
+
+
+def _resample_args(maps, n, src_shape=None):
+    """maps -> float64 [n][3][2] contiguous for vh_batch_resample_proton: one [3][2] map of (scale, offset)
+    per axis for every study, or one per study; every scale finite in [0.25, 4] and every offset finite
+    with |offset| <= 2^20.  ``src_shape`` (Rs, Cs, Zs), each 1..1024, is checked when given.  ValueError
+    for what the library would refuse, so the message names the argument."""
+    if src_shape is not None:
+        _shape3(src_shape, "resample: the source shape", RESAMPLE_MAX_SRC)
+    m = _real_array(maps, "resample: maps")
+    if m.shape not in ((3, 2), (n, 3, 2)):
+        raise ValueError(f"resample: {n} studies take a [3][2] map or one per study, got shape {m.shape}")
+    m = np.ascontiguousarray(np.broadcast_to(m, (n, 3, 2)))
+    s, o = m[..., 0], m[..., 1]
+    with np.errstate(invalid="ignore"):
+        ok = (s >= RESAMPLE_SCALE[0]) & (s <= RESAMPLE_SCALE[1]) & (np.abs(o) <= RESAMPLE_MAX_OFFSET)
+    if not ok.all():
+        raise ValueError(f"resample: every scale in {list(RESAMPLE_SCALE)} and every |offset| <= 2^20, both finite "
+                         f"(studies {sorted(set(np.argwhere(~ok)[:, 0].tolist()))})")
+    return m
+
+
 def denoise_constants(sigma, strength=2.0, patch=1):
     """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
     sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
@@ -326,6 +403,11 @@ _SIGS = {
     "vh_batch_shift": ([_P, ct.c_int, _P], ct.c_int),
     "vh_batch_download_proton": ([_P, _P], ct.c_int),
     "vh_register": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_resample_taps": ([_I64, _I64, ct.c_double, ct.c_double, _P, _P, _P], ct.c_int),
+    "vh_batch_upload_proton_src": ([_P, _P, _P], ct.c_int),
+    "vh_batch_resample_proton": ([_P, _P], ct.c_int),
+    "vh_batch_download_proton_src": ([_P, _P], ct.c_int),
+    "vh_resample": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -777,6 +859,24 @@ def register(proton, hp, search=(4, 4, 1), apply=False, device=0):
     c.check(c.L.vh_register(c.h, _ptr(p), _ptr(x), R, C, Z, B, _ptr(se), _ptr(score), _ptr(best), _ptr(status),
                             _ptr(out)), "vh_register")
     return (best, score, status, out) if apply else (best, score, status)
+
+
+def resample(src, dst_shape, maps, device=0):
+    """Volumes resampled from their own grid onto another from host arrays (vh_resample; the spec is in
+    include/vent_hip.h): ``src`` a 3-D volume or a 4-D batch of one shape, ``dst_shape`` (R, C, Z),
+    ``maps`` one [3][2] map of (scale, offset) per axis (grid_map makes one) or one per study.  Returns
+    float32 [B][R][C][Z]."""
+    x = as_batch(src, np.float32)
+    B = x.shape[0]
+    R, C, Z = _shape3(dst_shape, "resample: dst_shape")
+    if R < 2 or C < 2:
+        raise ValueError(f"resample: dst_shape needs R >= 2 and C >= 2, got {dst_shape!r}")
+    m = _resample_args(maps, B, x.shape[1:])   # (before any device call)
+    c = context(device)
+    shape = np.asarray(x.shape[1:], np.int64)
+    out = np.empty((B, R, C, Z), np.float32)
+    c.check(c.L.vh_resample(c.h, _ptr(x), _ptr(shape), R, C, Z, B, _ptr(m), _ptr(out)), "vh_resample")
+    return out
 
 
 def ci(defect, table, minvox, device=0, shell=True, out=None):
@@ -1265,6 +1365,35 @@ class Batch:
         """The resident proton as it stands (vh_batch_download_proton), float32 [B][R][C][Z]."""
         out = np.empty(self.shape, np.float32)
         self.ctx.check(self.L.vh_batch_download_proton(self.h, _ptr(out)), "vh_batch_download_proton")
+        return out
+
+    def upload_proton_src(self, src):
+        """The proton volumes on a grid of their own, float32 [B][Rs][Cs][Zs] with each dimension 1..1024
+        (vh_batch_upload_proton_src): resident in a buffer of their own until the next such upload, so they
+        can be resampled again with another map.  Invalidates nothing."""
+        s = np.ascontiguousarray(src, dtype=np.float32)
+        if s.ndim != 4 or s.shape[0] != self.shape[0]:
+            raise ValueError(f"batch expects ({self.shape[0]}, Rs, Cs, Zs), got {s.shape}")
+        shape = np.asarray(_shape3(s.shape[1:], "upload_proton_src: the source shape", RESAMPLE_MAX_SRC), np.int64)
+        self.ctx.check(self.L.vh_batch_upload_proton_src(self.h, _ptr(s), _ptr(shape)), "vh_batch_upload_proton_src")
+        self._src_shape = s.shape
+
+    def resample_proton(self, maps):
+        """Enqueue the resampling of the resident source onto the batch's grid (vh_batch_resample_proton; the
+        spec is in include/vent_hip.h): the resident proton becomes the result, as after upload_proton().
+        ``maps`` is one [3][2] map of (scale, offset) per axis (grid_map makes one) or one per study.
+        Invalidates nothing else.  Returns the maps used, float64 [B][3][2]."""
+        m = _resample_args(maps, self.shape[0])   # (before any device call)
+        self.ctx.check(self.L.vh_batch_resample_proton(self.h, _ptr(m)), "vh_batch_resample_proton")
+        return m
+
+    def download_proton_src(self):
+        """The resident source as it stands (vh_batch_download_proton_src), float32 [B][Rs][Cs][Zs]."""
+        shape = getattr(self, "_src_shape", None)
+        if shape is None:
+            raise ValueError("download_proton_src: no proton source resident: upload_proton_src first")
+        out = np.empty(shape, np.float32)
+        self.ctx.check(self.L.vh_batch_download_proton_src(self.h, _ptr(out)), "vh_batch_download_proton_src")
         return out
 
     def cohort_hist(self):

@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "vh_internal.h"
+#include "resample_host.h"
 
 // ---------------------------------------------------------------------------------------------
 // timing
@@ -1694,6 +1695,113 @@ int vh_register(vh_ctx *ctx, const float *proton, const float *hp, int64_t R, in
             batch_shift(b, VH_SHIFT_PROTON, best);
             d2h_on_stream(b, shifted_out, b->d_proton, sizeof(float) * (size_t)batch * b->V);
         }
+    })
+}
+
+// ---- the proton resampled from its own grid onto the batch's (resample.hip) -----------------------
+// The tap table of one axis, on the host alone (resample_host.h).
+int vh_resample_taps(int64_t n_src, int64_t n_dst, double scale, double offset, int32_t *first, int32_t *count,
+                     float *weight) {
+    return rs_axis_taps(n_src, n_dst, scale, offset, first, count, weight) ? VH_OK : VH_ERR_ARG;
+}
+
+// the argument checks of a resampling (host only: nothing is enqueued before they pass)
+static void check_resample_shape(const int64_t *shape) {
+    if (!shape) throw VhError{VH_ERR_ARG, "null shape"};
+    for (int k = 0; k < 3; ++k)
+        if (shape[k] < 1 || shape[k] > RS_MAX_SRC)
+            throw VhError{VH_ERR_ARG, "every source dimension must be 1..1024"};
+}
+static void check_resample_map(const double *map, int64_t nb) {
+    if (!map) throw VhError{VH_ERR_ARG, "null map"};
+    for (int64_t i = 0; i < nb; ++i)
+        for (int a = 0; a < 3; ++a)
+            if (!rs_map_in_limits(map[6 * i + 2 * a], map[6 * i + 2 * a + 1]))
+                throw VhError{VH_ERR_ARG, "every scale must be in [0.25, 4] and every |offset| <= 2^20, both finite (study " +
+                                              std::to_string(i) + ")"};
+}
+
+static void batch_upload_proton_src(vh_batch *b, const float *src, const int64_t *shape) {
+    const size_t n = (size_t)b->nb * (size_t)(shape[0] * shape[1] * shape[2]);
+    // no source resident until the new one has arrived whole: a failed growth or copy leaves none
+    b->rs_shape[0] = b->rs_shape[1] = b->rs_shape[2] = 0;
+    b->d_proton_src.reserve(n);
+    HIP_TRY(hipMemcpyAsync(b->d_proton_src, src, sizeof(float) * n, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    std::copy(shape, shape + 3, b->rs_shape);
+    b->state.proton_src_uploaded();
+}
+
+static void need_proton_src(const vh_batch *b) {
+    b->state.need_proton_src();
+    if (b->rs_shape[0] < 1) throw VhError{VH_ERR_ARG, "no proton source resident: its last upload failed"};
+}
+
+// The nb x 3 tables on the host, their upload, and the resampling of d_proton_src into d_proton.
+static void batch_resample_proton(vh_batch *b, const double *map) {
+    need_proton_src(b);
+    const int64_t dim[3] = {b->R, b->C, b->Z};
+    const int64_t stride = 10 * (b->R + b->C + b->Z);
+    std::vector<int32_t> tab((size_t)(b->nb * stride));
+    for (int64_t q = 0; q < b->nb; ++q) {
+        int32_t *t = tab.data() + q * stride;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t n = dim[a];
+            if (!rs_axis_taps(b->rs_shape[a], n, map[6 * q + 2 * a], map[6 * q + 2 * a + 1], t, t + n,
+                              reinterpret_cast<float *>(t + 2 * n)))
+                throw VhError{VH_ERR_ARG, "resample: a dimension of the batch is above 2^20"};
+            t += 10 * n;
+        }
+    }
+    RsPlan plan;
+    if (!vh_resample_plan(b, b->rs_shape, tab.data(), plan))
+        throw VhError{VH_ERR_ARG, "resample: more than 65535 studies"};
+    b->d_rs_tab.reserve(tab.size());
+    b->d_proton.reserve((size_t)b->nb * b->V);
+    // (pageable source: the copy has left tab when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_rs_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, b->stream));
+    vh_resample_launch(b, plan, b->d_proton_src, b->d_proton, b->d_rs_tab);
+    b->state.proton_uploaded();
+}
+
+int vh_batch_upload_proton_src(vh_batch *b, const float *src, const int64_t shape[3]) {
+    BATCH_TRY(b, {
+        if (!src) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_resample_shape(shape);
+        batch_upload_proton_src(b, src, shape);
+    })
+}
+
+int vh_batch_resample_proton(vh_batch *b, const double *map) {
+    BATCH_TRY(b, {
+        check_resample_map(map, b->nb);
+        batch_resample_proton(b, map);
+    })
+}
+
+int vh_batch_download_proton_src(vh_batch *b, float *src) {
+    BATCH_TRY(b, {
+        if (!src) throw VhError{VH_ERR_ARG, "null buffer"};
+        need_proton_src(b);
+        d2h_on_stream(b, src, b->d_proton_src,
+                      sizeof(float) * (size_t)b->nb * (size_t)(b->rs_shape[0] * b->rs_shape[1] * b->rs_shape[2]));
+    })
+}
+
+int vh_resample(vh_ctx *ctx, const float *src, const int64_t src_shape[3], int64_t R, int64_t C, int64_t Z,
+                int64_t batch, const double *map, float *out) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!src || !out) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_resample_shape(src_shape);
+        check_resample_map(map, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload_proton_src(b, src, src_shape);
+        batch_resample_proton(b, map);
+        d2h_on_stream(b, out, b->d_proton, sizeof(float) * (size_t)batch * b->V);
     })
 }
 

@@ -32,6 +32,7 @@ public:
         int32_t dist_bins = 0;       // its n_bins (while distribution)
         // an input, like the resident HPvent and mask: no transition but its own changes it
         bool proton = false;         // d_proton holds the batch's proton volumes
+        bool proton_src = false;     // d_proton_src holds the proton on its own grid (vh_batch_upload_proton_src)
     };
 
     // ---- transitions.  An uploaded defect map and a present CI survive ran and forgot_run; a cached
@@ -47,6 +48,7 @@ public:
     void montage_enqueued() { f_.montage = true; }
     void distribution_enqueued(int32_t bins) { f_.distribution = true; f_.dist_bins = bins; }
     void proton_uploaded() { f_.proton = true; }
+    void proton_src_uploaded() { f_.proton_src = true; }
 
     // ---- guards: VH_ERR_ARG, for the entry point to raise before it enqueues anything ----
     void need_run() const { need(f_.result, "vh_batch_run has not been called"); }
@@ -64,11 +66,15 @@ public:
         need(f_.distribution, "vh_batch_distribution has not been called since the last run");
     }
     void need_proton() const { need(f_.proton, "no proton resident: vh_batch_upload_proton first"); }
+    void need_proton_src() const {
+        need(f_.proton_src, "no proton source resident: vh_batch_upload_proton_src first");
+    }
 
     // ---- queries ----
     bool has_run() const { return f_.result; }
     bool layout_is_cached() const { return f_.layout; }
     bool has_proton() const { return f_.proton; }
+    bool has_proton_src() const { return f_.proton_src; }
     bool ci_is_fresh() const { return f_.ci_fresh; }
     bool selection_on() const { return f_.selection; }
     bool labels_valid() const { return f_.labels; }

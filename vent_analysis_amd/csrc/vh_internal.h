@@ -300,6 +300,10 @@ struct vh_batch {
     int64_t rg_ns = 0;               // its shifts; 0 before any register call
     Buf<int32_t> d_rg_shift;         // [nb][3] the last shift call's shifts
     Buf<float> d_rg_ptmp;            // [nb][V] the proton shift's destination, exchanged with d_proton
+    // vh_batch_upload_proton_src / vh_batch_resample_proton (resample.hip): on first demand
+    Buf<float> d_proton_src;         // [nb][rs_shape] the proton on its own grid, while state.has_proton_src()
+    int64_t rs_shape[3] = {0, 0, 0}; // its shape (Rs, Cs, Zs)
+    Buf<int32_t> d_rs_tab;           // [nb][10 (R + C + Z)] the last resampling's tap tables (RsTabs)
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -543,6 +547,21 @@ void vh_register_launch(vh_batch *b, const float *proton, const float *hp, const
 void vh_register_score_launch(vh_batch *b, const uint32_t *d_hist, const uint32_t *d_maxb, int ns, double *d_score);
 void vh_shift_launch_f32(vh_batch *b, const float *src, float *dst, const int32_t *d_shift);
 void vh_shift_launch_u8(vh_batch *b, const uint8_t *src, uint8_t *dst, const int32_t *d_shift);
+// resample.hip: the tap tables of one study's map as the kernel reads them, 10 (R + C + Z) words: for
+// each axis a of n = R, C, Z in turn first int32 [n], count int32 [n], weight float [n][8].
+// vh_resample_plan picks the tile and the band from the tables of the whole batch (host copy, [nb] such
+// blocks) and says whether the grid fits; vh_resample_launch: dst [nb][R][C][Z] = the resampling of src
+// [nb][Rs][Cs][Zs] with d_tab, the device copy of the same tables
+struct RsPlan {
+    int Rs, Cs, Zs;      // the source shape
+    int TC, TZ;          // destination columns and slices of a workgroup's tile
+    int BR;              // destination rows of its band
+    int span;            // source rows staged for a band: the largest over studies and bands
+    int ntc, ntz, nbands;
+    int kc, kz;          // the most c-taps of a column and z-taps of a slice in the batch
+};
+bool vh_resample_plan(const vh_batch *b, const int64_t src_shape[3], const int32_t *h_tab, RsPlan &p);
+void vh_resample_launch(vh_batch *b, const RsPlan &p, const float *src, float *dst, const int32_t *d_tab);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
