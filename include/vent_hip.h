@@ -40,6 +40,11 @@
  *                Vent_Analysis.py:1019-1026), all six linear-binning class counts (:256; the reference
  *                reports classes 1+2 only, :257) and the slice-wise mask / defect counts, per study from
  *                the resident buffers (build-defined); kernel-timing class "dist_b", not listed either
+ *   vh_batch_heterogeneity / vh_batch_download_heterogeneity / vh_heterogeneity  the local
+ *                coefficient of variation of the masked signal in a small in-plane window, as a map
+ *                specified to the last bit and as exact integer counts whose mean is the ventilation
+ *                heterogeneity index, per study from the resident buffers (build-defined);
+ *                kernel-timing class "het_b", not listed
  *   vh_batch_noise_sigma / vh_batch_denoise / vh_batch_download_hp / vh_noise_sigma / vh_denoise
  *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
  *                non-local-means filter of the resident HPvent, specified to the last bit, and the
@@ -367,6 +372,60 @@ int vh_batch_download_distribution(vh_batch *b, uint32_t *hist /* [nb][n_bins] *
 int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R, int64_t C, int64_t Z,
                     int64_t batch, float thresh, int norm, int32_t n_bins, float hi,
                     uint32_t *hist, int64_t *outside, int64_t *slice_counts);
+
+/* ---- the local ventilation heterogeneity of a device-resident batch ------------------------------
+ * The coefficient of variation (CoV) of the signal over the masked pixels of a small in-plane window,
+ * as a map, and its summary per study: a histogram, three counts and a fixed-point sum whose mean is
+ * the "ventilation heterogeneity index".  Every operation of the map is a correctly-rounded float32
+ * add, subtract, multiply, divide or square root in a fixed order (no fused multiply-add), so the map
+ * is specified to the last bit (tests/heterogeneity_ref.py is the same arithmetic in numpy); every
+ * count of the summary is an exact integer, so it does not depend on the order in which threads add.
+ *
+ * One study is x (float32 [R][C][Z], the slice axis fastest); every slice is processed on its own, for
+ * the reason given for the denoise filter below.  Parameters: radius k (1..5), min_count (2..(2k+1)^2),
+ * n_bins (1..1024), hi (finite, 0 < hi <= 16), exclude_defect (0 or 1).
+ *
+ * The effective mask: M(r, c, z) = (mask != 0), and with exclude_defect also (defect == 0), the
+ * resident defect map taken as it stands (the run's, vh_batch_set_defect's or vh_batch_select_defect's).
+ *
+ * For every voxel with M set, the window offsets (dr, dc) run in raster order, dr outer, each from -k
+ * to k.  A neighbour counts when it lies inside the slice and M is set there: there is no clamping and
+ * no padding value.
+ *   n = the number of counted neighbours (the voxel itself is one)
+ *   s = +0; for each counted neighbour in order: s = s + x
+ *   m = s / (float)n
+ *   q = +0; for each counted neighbour in order: t = x - m;  q = q + t*t   (multiply and add rounded separately)
+ * The voxel has a value when n >= min_count and m > 0; then cv = sqrtf(q / (float)(n - 1)) / m.
+ *
+ * The map, float32 [R][C][Z]: +0 where M is clear, -1 where M is set but there is no value, cv
+ * otherwise.  Non-finite input voxels follow the same pointwise rules: nothing special-cases them.
+ *
+ * The summary, over the voxels with a value: if cv < hi the voxel goes to bin
+ * min(n_bins - 1, (int)float32(cv * scale)), with scale = (float)n_bins / hi computed once in float32
+ * (the distribution's rule), and adds (int64)float32(cv * 16777216.0f) to a fixed-point sum (the product
+ * is exact and below 2^28 because hi <= 16; the conversion truncates); every other valued voxel, NaN
+ * included, is counted in n_over.  stats[i] = n_in, n_over, n_none (M set, no value), sum_fx;
+ * n_in + n_over + n_none is the number of voxels with M set, and an empty mask gives zeros throughout.
+ * The index is sum_fx / 2^24 / n_in, for the caller to compute in double (NaN when n_in == 0).
+ *
+ * vh_batch_heterogeneity enqueues only.  It reads the volume the last run's chain read (N4, or HPvent
+ * when do_n4 = 0), the resident mask and, with exclude_defect, the resident defect map, and changes
+ * nothing any other call wrote.  It may be called again with other parameters: the download returns
+ * the last call's result; a new run, and whatever forgets the run (vh_batch_denoise, the mask edits,
+ * ...), discards it.  VH_ERR_ARG, with nothing enqueued: a null batch, no vh_batch_run yet, any
+ * parameter outside the ranges above (and a batch of more than 65535 studies).
+ * vh_batch_download_heterogeneity waits; VH_ERR_ARG when vh_batch_heterogeneity has not been enqueued
+ * since the last run.  Its kernel-timing class is "het_b" (vh_batch_kernel_time reads it;
+ * vh_batch_kernel_names does not list it).
+ *
+ * vh_heterogeneity is the host-buffer form on the context's scratch batch, for any volume and mask:
+ * no run, no N4 and no chain behind it; a caller who wants to exclude defects ANDs them out of the mask. */
+int vh_batch_heterogeneity(vh_batch *b, int radius, int32_t min_count, int32_t n_bins, float hi, int exclude_defect);
+int vh_batch_download_heterogeneity(vh_batch *b, float *map /* [nb][R][C][Z] */, uint32_t *hist /* [nb][n_bins] */,
+                                    int64_t *stats /* [nb][4] */);   /* all nullable */
+int vh_heterogeneity(vh_ctx *ctx, const float *x, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                     int radius, int32_t min_count, int32_t n_bins, float hi,
+                     float *map, uint32_t *hist, int64_t *stats);
 
 /* ---- the denoise option of a device-resident batch ("Denoise Option", Vent_Analysis.py:1025) -------
  * An in-plane non-local-means filter of the resident HPvent with a Tukey bisquare weight.  Every

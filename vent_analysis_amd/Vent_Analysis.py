@@ -283,6 +283,26 @@ class Vent_Analysis:
             out['vdp_from_slices'] = 100 * np.float64(sl[:, 1].sum()) / n_mask
         return out
 
+    def ventilation_heterogeneity(self, radius=1, min_count=None, bins=100, hi=1.0, exclude_defect=False):
+        """The local ventilation heterogeneity (build-defined): the coefficient of variation of
+        N4HPvent over the masked pixels of the (2 ``radius`` + 1)^2 in-plane window of every masked
+        voxel that has at least ``min_count`` of them (None: a majority of the window), on the GPU, as
+        a map and as its mean over the lung, the ventilation heterogeneity index.  ``exclude_defect``
+        takes the voxels of ``defectArray`` as it stands (select_defect's map included) out of the mask.
+        Needs calculate_VDP first.  Returns a dict and sets nothing on the object: ``map`` float32
+        [R][C][Z] (+0 off the mask, -1 where there is no value, else the CoV); ``hist`` uint32 [bins]
+        over [0, ``hi``); ``edges`` float64 [bins + 1]; ``stats`` int64 [4] (voxels below hi, at or above
+        it, without a value, and the fixed-point sum); ``index``, the mean CoV of the voxels below hi."""
+        if isinstance(self.N4HPvent, str) or (exclude_defect and isinstance(self.defectArray, str)):
+            raise ValueError("ventilation_heterogeneity: N4HPvent / defectArray are not set "
+                             "(run calculate_VDP first)")
+        m = np.asarray(self.mask) != 0
+        if exclude_defect:
+            m = m & (np.asarray(self.defectArray) == 0)
+        out = _lib.heterogeneity(np.asarray(self.N4HPvent, dtype=np.float32), m, radius=radius,
+                                 min_count=min_count, bins=bins, hi=hi, device=self.device)
+        return {k: (v if k == 'edges' else v[0]) for k, v in out.items()}
+
     def estimate_noise(self, A=None):
         """The noise sigma of ``A`` (default ``self.HPvent``) for denoise (build-defined): float32
         sqrt(sum(A^2) / (2 N)) over the voxels calculate_SNR counts as noise for ``self.mask`` -- the

@@ -381,6 +381,10 @@ _SIGS = {
     "vh_batch_download_distribution": ([_P, _P, _P, _P], ct.c_int),
     "vh_distribution": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_float, ct.c_int, ct.c_int32, ct.c_float,
                          _P, _P, _P], ct.c_int),
+    "vh_batch_heterogeneity": ([_P, ct.c_int, ct.c_int32, ct.c_int32, ct.c_float, ct.c_int], ct.c_int),
+    "vh_batch_download_heterogeneity": ([_P, _P, _P, _P], ct.c_int),
+    "vh_heterogeneity": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_int, ct.c_int32, ct.c_int32, ct.c_float,
+                          _P, _P, _P], ct.c_int),
     "vh_batch_noise_sigma": ([_P, _P], ct.c_int),
     "vh_batch_denoise": ([_P, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int], ct.c_int),
     "vh_batch_download_hp": ([_P, _P], ct.c_int),
@@ -755,6 +759,60 @@ def distribution(n4, mask, norm="p99", bins=1024, hi=1.5, thresh=0.6, device=0):
     c.check(c.L.vh_distribution(c.h, _ptr(n), _ptr(m), R, C, Z, B, ct.c_float(thresh), norm_source(norm),
                                 bins, ct.c_float(hi), _ptr(hist), _ptr(outside), _ptr(sl)), "vh_distribution")
     return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
+
+
+def _heterogeneity_args(radius, min_count, bins, hi):
+    """The checked (radius, min_count, bins, hi) of vh_batch_heterogeneity; ``min_count`` None is the
+    majority of the window, (2 radius + 1)^2 // 2 + 1.  ValueError for what the library would refuse,
+    so the message names the argument."""
+    def whole(v, what):
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"heterogeneity: {what} is an int, got {v!r}")
+        return int(v)
+    radius = whole(radius, "radius")
+    if not 1 <= radius <= 5:
+        raise ValueError(f"heterogeneity: radius must be 1..5, got {radius!r}")
+    win = (2 * radius + 1) ** 2
+    min_count = win // 2 + 1 if min_count is None else whole(min_count, "min_count")
+    if not 2 <= min_count <= win:
+        raise ValueError(f"heterogeneity: min_count must be 2..{win} at radius {radius}, got {min_count!r}")
+    bins = whole(bins, "bins")
+    if not 1 <= bins <= 1024:
+        raise ValueError(f"heterogeneity: bins must be 1..1024, got {bins!r}")
+    h = np.float32(hi)
+    if not (np.isfinite(h) and 0 < h <= 16):
+        raise ValueError(f"heterogeneity: hi must be finite, > 0 and <= 16, got {hi!r}")
+    return radius, min_count, bins, float(h)
+
+
+def het_index(stats):
+    """The ventilation heterogeneity index of each study from its ``stats`` row(s) (n_in, n_over,
+    n_none, sum_fx): float64 sum_fx / 2^24 / n_in, the mean CoV over the in-range voxels; NaN where
+    n_in == 0."""
+    st = np.asarray(stats, dtype=np.int64)
+    n_in = st[..., 0].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n_in > 0, st[..., 3].astype(np.float64) / 16777216.0 / n_in, np.nan)
+
+
+def heterogeneity(x, mask, radius=1, min_count=None, bins=100, hi=1.0, device=0):
+    """The local ventilation heterogeneity from host arrays (vh_heterogeneity; the spec is in
+    include/vent_hip.h): ``x`` a 3-D volume or a 4-D batch, ``mask`` of the same shape and any dtype,
+    nonzero counting as set.  No run and no N4 behind it; to exclude defects, AND them out of the mask.
+    Returns the dict of Batch.download_heterogeneity."""
+    c = context(device)
+    v = as_batch(x, np.float32)
+    m = as_batch(_mask_u8(mask), np.uint8)
+    if v.shape != m.shape:
+        raise ValueError("volume and mask shapes differ")
+    radius, min_count, bins, hi = _heterogeneity_args(radius, min_count, bins, hi)
+    B, R, C, Z = v.shape
+    out = np.empty_like(v)
+    hist = np.zeros((B, bins), np.uint32)
+    stats = np.zeros((B, 4), np.int64)
+    c.check(c.L.vh_heterogeneity(c.h, _ptr(v), _ptr(m), R, C, Z, B, radius, min_count, bins, ct.c_float(hi),
+                                 _ptr(out), _ptr(hist), _ptr(stats)), "vh_heterogeneity")
+    return dict(map=out, hist=hist, edges=dist_edges(bins, hi), stats=stats, index=het_index(stats))
 
 
 def _denoise_args(sigma, n, strength, search, patch):
@@ -1216,6 +1274,34 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_distribution(self.h, _ptr(hist), _ptr(outside), _ptr(sl)),
                        "vh_batch_download_distribution")
         return dict(hist=hist, outside=outside, slice_counts=sl, edges=dist_edges(bins, hi))
+
+    def heterogeneity(self, radius=1, min_count=None, bins=100, hi=1.0, exclude_defect=False):
+        """Enqueue the local ventilation heterogeneity of every study (vh_batch_heterogeneity; the
+        spec is in include/vent_hip.h): the coefficient of variation of the volume the last run's chain
+        read over the masked pixels of the (2 radius + 1)^2 in-plane window, where at least
+        ``min_count`` (None: a majority of the window) of them are set, and its histogram in ``bins``
+        bins of [0, hi).  ``exclude_defect`` takes the resident defect map's voxels out of the mask.
+        Read-only; download_heterogeneity fetches the last call's result.  Needs a run."""
+        radius, min_count, bins, hi = _heterogeneity_args(radius, min_count, bins, hi)
+        self.ctx.check(self.L.vh_batch_heterogeneity(self.h, radius, min_count, bins, ct.c_float(hi),
+                                                     int(bool(exclude_defect))), "vh_batch_heterogeneity")
+        self._het = (bins, hi)
+
+    def download_heterogeneity(self, map=True):
+        """The last heterogeneity() as a dict: ``map`` float32 [B][R][C][Z] (+0 off the mask, -1 where
+        the mask is set but there is no value, else the CoV; None with ``map=False``: only counts come
+        back); ``hist`` uint32 [B][bins]; ``edges`` float64 [bins + 1], for display; ``stats`` int64
+        [B][4]: n_in, n_over (at or above hi, NaN included), n_none, sum_fx; ``index`` float64 [B],
+        het_index(stats)."""
+        bins, hi = getattr(self, "_het", (0, 1.0))
+        B = self.shape[0]
+        out = np.empty(self.shape, np.float32) if map else None
+        hist = np.zeros((B, bins), np.uint32)
+        stats = np.zeros((B, 4), np.int64)
+        self.ctx.check(self.L.vh_batch_download_heterogeneity(self.h, _ptr(out), _ptr(hist), _ptr(stats)),
+                       "vh_batch_download_heterogeneity")
+        return dict(map=out, hist=hist, edges=dist_edges(bins, hi) if bins else None, stats=stats,
+                    index=het_index(stats))
 
     def noise_sigma(self):
         """float32 [B]: the noise of each resident HPvent (vh_batch_noise_sigma), sqrt(S2 / (2 N))

@@ -1142,6 +1142,76 @@ int vh_distribution(vh_ctx *ctx, const float *n4, const uint8_t *mask, int64_t R
     })
 }
 
+// ---- the local ventilation heterogeneity of a device-resident batch (heterogeneity.hip) -----------
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_heterogeneity(int radius, int32_t min_count, int32_t n_bins, float hi) {
+    if (radius < 1 || radius > 5) throw VhError{VH_ERR_ARG, "radius must be 1..5"};
+    const int32_t win = (2 * radius + 1) * (2 * radius + 1);
+    if (min_count < 2 || min_count > win) throw VhError{VH_ERR_ARG, "min_count must be 2..(2 radius + 1)^2"};
+    if (n_bins < 1 || n_bins > VH_COHORT_BINS) throw VhError{VH_ERR_ARG, "n_bins must be 1..1024"};
+    if (!std::isfinite(hi) || !(hi > 0.0f) || !(hi <= 16.0f))
+        throw VhError{VH_ERR_ARG, "hi must be finite, > 0 and <= 16"};
+}
+
+// Enqueue the sweep over src (a volume of the batch) and the resident mask, without the voxels of
+// defect (nullable).  It writes its own three buffers only, so nothing another call on the batch reads
+// changes (the CI stays fresh).
+static void batch_heterogeneity(vh_batch *b, const float *src, const uint8_t *defect, int radius, int32_t min_count,
+                                int32_t n_bins, float hi) {
+    if (!vh_het_takes(b)) throw VhError{VH_ERR_ARG, "heterogeneity: batch or tile count out of range"};
+    b->d_het.reserve((size_t)b->nb * b->V);
+    b->d_het_hist.reserve((size_t)b->nb * VH_COHORT_BINS);   // the largest n_bins: no regrowth
+    b->d_het_stats.reserve((size_t)b->nb * 4);
+    const float scale = (float)n_bins / hi;   // once, in float32: the kernel multiplies by it
+    vh_het_launch(b, src, defect, b->d_het, b->d_het_hist, b->d_het_stats, radius, min_count, n_bins, hi, scale);
+    b->state.heterogeneity_enqueued(n_bins);
+}
+
+static void batch_download_heterogeneity(vh_batch *b, float *map, uint32_t *hist, int64_t *stats) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (map) HIP_TRY(hipMemcpyAsync(map, b->d_het, sizeof(float) * nb * b->V, hipMemcpyDeviceToHost, st));
+    if (hist)
+        HIP_TRY(hipMemcpyAsync(hist, b->d_het_hist, sizeof(uint32_t) * nb * b->state.het_bins(), hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, b->d_het_stats, sizeof(int64_t) * nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_heterogeneity(vh_batch *b, int radius, int32_t min_count, int32_t n_bins, float hi, int exclude_defect) {
+    BATCH_TRY(b, {
+        check_heterogeneity(radius, min_count, n_bins, hi);
+        if (exclude_defect != 0 && exclude_defect != 1) throw VhError{VH_ERR_ARG, "exclude_defect must be 0 or 1"};
+        b->state.need_run();
+        batch_heterogeneity(b, b->n4_last(), exclude_defect ? b->d_defect.get() : nullptr, radius, min_count, n_bins, hi);
+    })
+}
+
+int vh_batch_download_heterogeneity(vh_batch *b, float *map, uint32_t *hist, int64_t *stats) {
+    BATCH_TRY(b, {
+        b->state.need_heterogeneity();
+        batch_download_heterogeneity(b, map, hist, stats);
+    })
+}
+
+int vh_heterogeneity(vh_ctx *ctx, const float *x, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                     int radius, int32_t min_count, int32_t n_bins, float hi, float *map, uint32_t *hist,
+                     int64_t *stats) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!x || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_heterogeneity(radius, min_count, n_bins, hi);
+        check_dims(R, C, Z, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, x, mask);
+        b->state.forgot_run();   // (the scratch batch's volumes are no run's)
+        batch_heterogeneity(b, b->d_hp, nullptr, radius, min_count, n_bins, hi);
+        batch_download_heterogeneity(b, map, hist, stats);
+    })
+}
+
 // ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------
 // The resident HPvent, or the mask statistics and scalars, are no longer the last run's: the calls that
 // read a run's results refuse until the next one; an uploaded defect map and an enqueued CI stay.

@@ -282,6 +282,10 @@ struct vh_batch {
     // vh_batch_denoise / vh_batch_noise_sigma (denoise.hip): on first demand
     Buf<float> d_dn_prm;             // [nb][2] the last denoise's inv_h2 and bias of each study
     Buf<float> d_dn_sigma;           // [nb] the last noise estimate
+    // vh_batch_heterogeneity (heterogeneity.hip): every buffer on first demand
+    Buf<float> d_het;                // [nb][V] the last call's CoV maps
+    Buf<uint32_t> d_het_hist;        // [nb][state.het_bins()] its histograms
+    Buf<unsigned long long> d_het_stats;   // [nb][4] n_in, n_over, n_none, sum_fx
     // vh_batch_edit_mask / vh_batch_download_mask (mask_edit.hip): on first demand.  The edits' scratch
     // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
     Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
@@ -517,6 +521,12 @@ void vh_dist_launch(vh_batch *b, int norm, int n_bins, float hi, float scale);
 bool vh_denoise_takes(const vh_batch *b);
 void vh_denoise_launch(vh_batch *b, const float *src, float *dst, const float *d_prm, int S, int P, int rician);
 void vh_noise_sigma_launch(vh_batch *b, float *d_sigma);
+// heterogeneity.hip: the CoV map of every study of src (a volume of the batch) over the resident mask,
+// without the voxels of defect (nullable) != 0, into map [nb][V], with its summary in d_hist
+// [nb][n_bins] and d_stats [nb][4] (both zeroed here); vh_het_takes: the grid fits
+bool vh_het_takes(const vh_batch *b);
+void vh_het_launch(vh_batch *b, const float *src, const uint8_t *defect, float *map, uint32_t *d_hist,
+                   unsigned long long *d_stats, int K, int min_count, int n_bins, float hi, float scale);
 // mask_edit.hip: one disc dilation (erode 0) or erosion (erode 1) of every study, src -> dst (two
 // mask volumes of the batch), with d_radius [nb] in 0..5 (0: the study is copied);
 // vh_mask_edit_takes: the grid fits.  vh_mask_paint_launch: mask = paint(mask != 0, strokes != 0) in
