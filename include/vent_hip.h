@@ -45,6 +45,10 @@
  *                specified to the last bit and as exact integer counts whose mean is the ventilation
  *                heterogeneity index, per study from the resident buffers (build-defined);
  *                kernel-timing class "het_b", not listed
+ *   vh_batch_core_rind / vh_batch_download_core_rind / vh_core_rind / vh_core_rind_form  the core-rind
+ *                analysis: the exact squared in-plane distance of every mask voxel to the mask's edge,
+ *                as a map, and the mask and defect voxels of every depth band, per study from the
+ *                resident mask and defect map (build-defined); kernel-timing class "depth_b", not listed
  *   vh_batch_noise_sigma / vh_batch_denoise / vh_batch_download_hp / vh_noise_sigma / vh_denoise
  *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
  *                non-local-means filter of the resident HPvent, specified to the last bit, and the
@@ -426,6 +430,65 @@ int vh_batch_download_heterogeneity(vh_batch *b, float *map /* [nb][R][C][Z] */,
 int vh_heterogeneity(vh_ctx *ctx, const float *x, const uint8_t *mask, int64_t R, int64_t C, int64_t Z, int64_t batch,
                      int radius, int32_t min_count, int32_t n_bins, float hi,
                      float *map, uint32_t *hist, int64_t *stats);
+
+/* ---- the core-rind analysis of a device-resident batch --------------------------------------------
+ * Where in the lung the defects lie: at the periphery (the "rind" or "peel") or in the centre (the
+ * "core").  Per voxel of the mask the squared in-plane Euclidean distance to the mask's edge, as a
+ * map, and per study the mask voxels and the defect voxels of every depth band.  The squared distance
+ * is an integer and every summary is an integer count, so the result is exact and does not depend on
+ * the order in which threads add (tests/core_rind_ref.py is the same definition in numpy).
+ *
+ * One study is [R][C][Z], the slice axis fastest; every slice is processed on its own, for the reason
+ * given for the denoise filter below.
+ *
+ * The mask: M(r, c, z) = (mask != 0).  A position outside the slice counts as NOT in M: a lung cut by
+ * the field of view has an edge there.  This is deliberately unlike the erosion of vh_batch_edit_mask,
+ * which pads with 1; on a mask that stays k + 1 pixels off the slice border the two agree,
+ * {D2 > k^2} = erode(mask, k).
+ *
+ * The distance: for a voxel with M set, D2(r, c, z) = the minimum of (r - r')^2 + (c - c')^2 over the
+ * positions (r', c') of slice z with M clear, the one-pixel ring outside the slice included; 0 where
+ * M is clear.  So D2 >= 1 on the mask and D2 <= (min(R, C) / 2 + 1)^2.
+ *
+ * The map, uint16 [R][C][Z]: min(D2, 65535).  The value saturates; only planes of 510 or more on both
+ * sides can reach it.
+ *
+ * The bands: n_thr thresholds (0..31), integers 1 <= thr[0] < thr[1] < ... <= 65535, give n_thr + 1
+ * bands; a masked voxel's band is the number of thresholds <= min(D2, 65535).  Band 0 is the outermost
+ * rind.  (A depth of at least e pixels, D2 >= e^2, is D2 >= ceil(e^2): the caller rounds up.)
+ *
+ * The summary per study: counts int64 [n_thr + 1][2], the voxels of M in the band and those of them
+ * with defect != 0, the resident defect map taken as it stands at the enqueue (the run's,
+ * vh_batch_set_defect's or vh_batch_select_defect's): a later change of the map does not change them.
+ * stats int64 [2]: n_mask and the largest D2, unsaturated.  An empty mask gives zeros throughout.  With
+ * with_defect = 0 the defect column is 0 and no defect map is needed.
+ *
+ * vh_batch_core_rind enqueues only (thr is read before it returns).  It reads the resident mask and,
+ * with with_defect, the resident defect map, and changes nothing any other call wrote.  It may be
+ * called again with other thresholds: the download returns the last call's result; a new run, and
+ * whatever forgets the run (vh_batch_denoise, the mask edits, vh_batch_segment, ...), discards it.
+ * VH_ERR_ARG, with nothing enqueued: a null batch, n_thr outside 0..31, thresholds that are not
+ * strictly increasing or include 0, with_defect outside {0, 1}, with_defect with no defect maps
+ * resident (neither a run nor vh_batch_set_defect), a batch of more than 65535 studies.
+ * vh_batch_download_core_rind waits; every pointer is nullable; VH_ERR_ARG when vh_batch_core_rind
+ * has not been enqueued since the last run or the last call that forgets the run.  Its kernel-timing
+ * class is "depth_b" (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * The kernels take every shape a batch accepts.  The search has two forms, chosen by the shape alone:
+ * vh_core_rind_form returns 0 when the rows a workgroup searches are staged in LDS (a row of C Z
+ * column distances, bytes where R <= 510 and uint16 otherwise, within 60 KiB), 1 when a row is too
+ * long for that and the search reads them through the caches (-1 for a dimension below 1).  Both give
+ * the same result.
+ *
+ * vh_core_rind is the host-buffer form on the context's scratch batch, for any mask and (nullable)
+ * defect map: no run behind it. */
+int vh_batch_core_rind(vh_batch *b, const uint16_t *thr, int32_t n_thr, int with_defect);
+int vh_batch_download_core_rind(vh_batch *b, uint16_t *map /* [nb][R][C][Z] */, int64_t *counts /* [nb][n_thr+1][2] */,
+                                int64_t *stats /* [nb][2] */);   /* all nullable */
+int vh_core_rind(vh_ctx *ctx, const uint8_t *mask, const uint8_t *defect /* nullable */, int64_t R, int64_t C,
+                 int64_t Z, int64_t batch, const uint16_t *thr, int32_t n_thr,
+                 uint16_t *map, int64_t *counts, int64_t *stats);
+int vh_core_rind_form(int64_t R, int64_t C, int64_t Z);
 
 /* ---- the denoise option of a device-resident batch ("Denoise Option", Vent_Analysis.py:1025) -------
  * An in-plane non-local-means filter of the resident HPvent with a Tukey bisquare weight.  Every

@@ -303,6 +303,31 @@ class Vent_Analysis:
                                  min_count=min_count, bins=bins, hi=hi, device=self.device)
         return {k: (v if k == 'edges' else v[0]) for k, v in out.items()}
 
+    def core_rind(self, edges_mm=(3.0, 6.0), with_defect=True):
+        """The core-rind analysis (build-defined): how the mask and the defects divide between the
+        lung's periphery (the "rind") and its centre (the "core"), on the GPU.  Every voxel of
+        ``self.mask`` gets its in-plane depth, the exact Euclidean distance to the nearest pixel of its
+        slice off the mask (the slice border counts as one), and ``edges_mm`` (increasing, divided by
+        the in-plane pixel size ``self.vox[0]``; ValueError when ``vox[0] != vox[1]``) separates the
+        depth bands, band 0 the outermost.  ``with_defect`` counts ``defectArray`` as it stands
+        (select_defect's map included; needs calculate_VDP first).  Returns a dict and
+        sets nothing on the object: ``counts`` int64 [bands][2] (the band's mask voxels, its defect voxels);
+        ``band_vdp`` float64 [bands], NaN for an empty band; ``edges_mm``; ``thresholds`` uint16, the
+        squared pixel depths the bands start at; ``n_mask``; ``d2`` uint16 [R][C][Z], the squared
+        depth in pixels (saturated at 65535); ``depth_max_mm``, the deepest voxel's depth."""
+        if isinstance(getattr(self, 'mask', ''), str) or (with_defect and isinstance(self.defectArray, str)):
+            raise ValueError("core_rind: mask / defectArray are not set (run calculate_VDP first, or "
+                             "with_defect=False)")
+        if isinstance(self.vox, str) or float(self.vox[0]) != float(self.vox[1]):
+            raise ValueError(f"core_rind: the in-plane pixels must be square, got vox = {tuple(self.vox)!r}")
+        px = float(self.vox[0])
+        edges = np.atleast_1d(np.asarray(edges_mm, dtype=np.float64)) if np.size(edges_mm) else np.zeros(0)
+        out = _lib.core_rind(np.asarray(self.mask), np.asarray(self.defectArray) if with_defect else None,
+                             edges=edges / px, device=self.device)
+        return dict(counts=out['counts'][0], band_vdp=out['band_vdp'][0], edges_mm=edges,
+                    thresholds=out['thresholds'], n_mask=int(out['stats'][0, 0]), d2=out['d2'][0],
+                    depth_max_mm=px * float(np.sqrt(np.float64(out['stats'][0, 1]))))
+
     def estimate_noise(self, A=None):
         """The noise sigma of ``A`` (default ``self.HPvent``) for denoise (build-defined): float32
         sqrt(sum(A^2) / (2 N)) over the voxels calculate_SNR counts as noise for ``self.mask`` -- the

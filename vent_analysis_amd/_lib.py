@@ -385,6 +385,10 @@ _SIGS = {
     "vh_batch_download_heterogeneity": ([_P, _P, _P, _P], ct.c_int),
     "vh_heterogeneity": ([_P, _P, _P, _I64, _I64, _I64, _I64, ct.c_int, ct.c_int32, ct.c_int32, ct.c_float,
                           _P, _P, _P], ct.c_int),
+    "vh_batch_core_rind": ([_P, _P, ct.c_int32, ct.c_int], ct.c_int),
+    "vh_batch_download_core_rind": ([_P, _P, _P, _P], ct.c_int),
+    "vh_core_rind_form": ([_I64, _I64, _I64], ct.c_int),
+    "vh_core_rind": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, ct.c_int32, _P, _P, _P], ct.c_int),
     "vh_batch_noise_sigma": ([_P, _P], ct.c_int),
     "vh_batch_denoise": ([_P, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int], ct.c_int),
     "vh_batch_download_hp": ([_P, _P], ct.c_int),
@@ -813,6 +817,82 @@ def heterogeneity(x, mask, radius=1, min_count=None, bins=100, hi=1.0, device=0)
     c.check(c.L.vh_heterogeneity(c.h, _ptr(v), _ptr(m), R, C, Z, B, radius, min_count, bins, ct.c_float(hi),
                                  _ptr(out), _ptr(hist), _ptr(stats)), "vh_heterogeneity")
     return dict(map=out, hist=hist, edges=dist_edges(bins, hi), stats=stats, index=het_index(stats))
+
+
+def depth_thresholds(edges):
+    """Band edges in pixels (floats allowed), increasing -> the uint16 thresholds ceil(e * e) of
+    vh_batch_core_rind, computed in double: a voxel is at least e pixels deep, D2 >= e^2, exactly when
+    D2 >= ceil(e^2), D2 being an integer.  ValueError for an edge that is not finite or not > 0, for a
+    threshold above 65535, for thresholds that are not strictly increasing (two edges with one
+    threshold included) and for more than 31 edges."""
+    e = np.atleast_1d(np.asarray(edges, dtype=np.float64)) if np.size(edges) else np.zeros(0, np.float64)
+    if e.ndim != 1:
+        raise ValueError(f"core_rind: edges is a sequence of numbers, got shape {e.shape}")
+    if e.size > 31:
+        raise ValueError(f"core_rind: at most 31 edges, got {e.size}")
+    if not (np.isfinite(e).all() and (e > 0).all()):
+        raise ValueError(f"core_rind: every edge must be finite and > 0, got {edges!r}")
+    t = np.ceil(e * e)
+    if (t > 65535).any():
+        raise ValueError(f"core_rind: an edge's threshold ceil(e^2) exceeds 65535, got {edges!r}")
+    if (np.diff(t) <= 0).any():
+        raise ValueError(f"core_rind: the edges must give strictly increasing thresholds, got {t.astype(int).tolist()}")
+    return t.astype(np.uint16)
+
+
+def _core_rind_args(edges, thresholds):
+    """The uint16 thresholds of vh_batch_core_rind: depth_thresholds(edges), or ``thresholds`` (ints,
+    1 <= t[0] < t[1] < ... <= 65535, at most 31) as they are when given.  ValueError for what the
+    library would refuse, so the message names the argument."""
+    if thresholds is None:
+        return depth_thresholds(edges)
+    t = np.asarray(thresholds)
+    if t.size == 0:
+        return np.zeros(0, np.uint16)
+    if t.ndim != 1 or t.dtype == np.bool_ or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"core_rind: thresholds is a sequence of ints, got {thresholds!r}")
+    if t.size > 31:
+        raise ValueError(f"core_rind: at most 31 thresholds, got {t.size}")
+    t = t.astype(np.int64)
+    if t[0] < 1 or t[-1] > 65535 or (np.diff(t) <= 0).any():
+        raise ValueError(f"core_rind: thresholds must be strictly increasing in 1..65535, got {t.tolist()}")
+    return t.astype(np.uint16)
+
+
+def band_vdp(counts):
+    """float64 100 * defect / mask of each band from ``counts`` [...][2]; NaN for an empty band."""
+    c = np.asarray(counts, dtype=np.int64)
+    n = c[..., 0].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n > 0, 100.0 * c[..., 1].astype(np.float64) / n, np.nan)
+
+
+def core_rind_form(R, C, Z):
+    """'rows' or 'global': which form of the search a study shape takes (vh_core_rind_form; no device)."""
+    f = lib().vh_core_rind_form(int(R), int(C), int(Z))
+    if f not in (0, 1):
+        raise ValueError(f"core_rind_form: dims must be >= 1, got {(R, C, Z)!r}")
+    return ("rows", "global")[f]
+
+
+def core_rind(mask, defect=None, edges=(1.5, 3.5), device=0, thresholds=None):
+    """The core-rind analysis from host arrays (vh_core_rind; the spec is in include/vent_hip.h):
+    ``mask`` a 3-D volume or a 4-D batch of any dtype, nonzero counting as set; ``defect`` of the same
+    shape, or None for a defect column of 0.  No run behind it.  Returns the dict of
+    Batch.download_core_rind."""
+    thr = _core_rind_args(edges, thresholds)
+    m = as_batch(_mask_u8(mask), np.uint8)
+    d = None if defect is None else as_batch(_mask_u8(defect), np.uint8)
+    if d is not None and d.shape != m.shape:
+        raise ValueError("mask and defect shapes differ")
+    c = context(device)
+    B = m.shape[0]
+    out = np.empty(m.shape, np.uint16)
+    counts = np.zeros((B, thr.size + 1, 2), np.int64)
+    stats = np.zeros((B, 2), np.int64)
+    c.check(c.L.vh_core_rind(c.h, _ptr(m), _ptr(d), *m.shape[1:], B, _ptr(thr), thr.size,
+                             _ptr(out), _ptr(counts), _ptr(stats)), "vh_core_rind")
+    return dict(d2=out, counts=counts, stats=stats, thresholds=thr, band_vdp=band_vdp(counts))
 
 
 def _denoise_args(sigma, n, strength, search, patch):
@@ -1302,6 +1382,34 @@ class Batch:
                        "vh_batch_download_heterogeneity")
         return dict(map=out, hist=hist, edges=dist_edges(bins, hi) if bins else None, stats=stats,
                     index=het_index(stats))
+
+    def core_rind(self, edges=(1.5, 3.5), with_defect=True, thresholds=None):
+        """Enqueue the core-rind analysis of every study (vh_batch_core_rind; the spec is in
+        include/vent_hip.h): the exact squared in-plane distance D2 of every mask voxel to the mask's
+        edge (the slice border is an edge), and the mask and defect voxels of the depth bands that
+        ``edges`` (pixels, increasing; depth_thresholds) or ``thresholds`` (D2 values as they are)
+        separate, band 0 the outermost rind.  ``with_defect`` counts the resident defect map as it
+        stands (needs a run or upload_defect); without it the defect column is 0.  Read-only;
+        download_core_rind fetches the last call's result."""
+        thr = _core_rind_args(edges, thresholds)
+        self.ctx.check(self.L.vh_batch_core_rind(self.h, _ptr(thr), thr.size, int(bool(with_defect))),
+                       "vh_batch_core_rind")
+        self._cr = thr
+
+    def download_core_rind(self, map=True):
+        """The last core_rind() as a dict: ``d2`` uint16 [B][R][C][Z] = min(D2, 65535), 0 off the mask
+        (None with ``map=False``: only counts come back); ``counts`` int64 [B][bands][2], the band's mask
+        voxels and its defect voxels; ``stats`` int64 [B][2], n_mask and the largest D2 (unsaturated);
+        ``thresholds`` uint16 [bands - 1]; ``band_vdp`` float64 [B][bands], 100 * defect / mask, NaN
+        for an empty band."""
+        thr = getattr(self, "_cr", np.zeros(0, np.uint16))
+        B = self.shape[0]
+        out = np.empty(self.shape, np.uint16) if map else None
+        counts = np.zeros((B, thr.size + 1, 2), np.int64)
+        stats = np.zeros((B, 2), np.int64)
+        self.ctx.check(self.L.vh_batch_download_core_rind(self.h, _ptr(out), _ptr(counts), _ptr(stats)),
+                       "vh_batch_download_core_rind")
+        return dict(d2=out, counts=counts, stats=stats, thresholds=thr.copy(), band_vdp=band_vdp(counts))
 
     def noise_sigma(self):
         """float32 [B]: the noise of each resident HPvent (vh_batch_noise_sigma), sqrt(S2 / (2 N))

@@ -1212,6 +1212,80 @@ int vh_heterogeneity(vh_ctx *ctx, const float *x, const uint8_t *mask, int64_t R
     })
 }
 
+// ---- the core-rind analysis of a device-resident batch (depth.hip) ---------------------------------
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_core_rind(const uint16_t *thr, int32_t n_thr) {
+    if (n_thr < 0 || n_thr > 31) throw VhError{VH_ERR_ARG, "n_thr must be 0..31"};
+    if (n_thr > 0 && !thr) throw VhError{VH_ERR_ARG, "null thresholds"};
+    for (int32_t i = 0; i < n_thr; ++i)
+        if (thr[i] == 0 || (i > 0 && thr[i] <= thr[i - 1]))
+            throw VhError{VH_ERR_ARG, "thresholds must be strictly increasing and >= 1"};
+}
+
+// Enqueue the sweep over the resident mask, with the defect column from defect (nullable).  It writes
+// its own buffers only, so nothing another call on the batch reads changes (the CI stays fresh).
+static void batch_core_rind(vh_batch *b, const uint8_t *defect, const uint16_t *thr, int32_t n_thr) {
+    if (!vh_depth_takes(b)) throw VhError{VH_ERR_ARG, "core_rind: more than 65535 studies"};
+    b->d_cr_map.reserve((size_t)b->nb * b->V);
+    b->d_cr_g.reserve((size_t)b->nb * b->V);
+    b->d_cr_counts.reserve((size_t)b->nb * 64);   // the largest n_thr: no regrowth
+    b->d_cr_stats.reserve((size_t)b->nb * 2);
+    vh_depth_launch(b, defect, thr, n_thr, b->d_cr_g, b->d_cr_map, b->d_cr_counts, b->d_cr_stats);
+    b->state.core_rind_enqueued(n_thr + 1);
+}
+
+static void batch_download_core_rind(vh_batch *b, uint16_t *map, int64_t *counts, int64_t *stats) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (map) HIP_TRY(hipMemcpyAsync(map, b->d_cr_map, sizeof(uint16_t) * nb * b->V, hipMemcpyDeviceToHost, st));
+    if (counts)
+        HIP_TRY(hipMemcpyAsync(counts, b->d_cr_counts, sizeof(int64_t) * nb * 2 * b->state.cr_bands(),
+                               hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, b->d_cr_stats, sizeof(int64_t) * nb * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_core_rind(vh_batch *b, const uint16_t *thr, int32_t n_thr, int with_defect) {
+    BATCH_TRY(b, {
+        check_core_rind(thr, n_thr);
+        if (with_defect != 0 && with_defect != 1) throw VhError{VH_ERR_ARG, "with_defect must be 0 or 1"};
+        if (with_defect) b->state.need_defect();
+        batch_core_rind(b, with_defect ? b->d_defect.get() : nullptr, thr, n_thr);
+    })
+}
+
+int vh_batch_download_core_rind(vh_batch *b, uint16_t *map, int64_t *counts, int64_t *stats) {
+    BATCH_TRY(b, {
+        b->state.need_core_rind();
+        batch_download_core_rind(b, map, counts, stats);
+    })
+}
+
+int vh_core_rind_form(int64_t R, int64_t C, int64_t Z) {
+    if (R < 1 || C < 1 || Z < 1) return -1;
+    return vh_depth_form(R, C, Z);
+}
+
+int vh_core_rind(vh_ctx *ctx, const uint8_t *mask, const uint8_t *defect, int64_t R, int64_t C, int64_t Z, int64_t batch,
+                 const uint16_t *thr, int32_t n_thr, uint16_t *map, int64_t *counts, int64_t *stats) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_core_rind(thr, n_thr);
+        check_dims(R, C, Z, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, nullptr, mask);
+        if (defect)   // (pageable source, and batch_download_core_rind waits before the call returns)
+            HIP_TRY(hipMemcpyAsync(b->d_defect, defect, (size_t)batch * b->V, hipMemcpyHostToDevice, b->stream));
+        b->state.forgot_run();   // (the scratch batch's volumes are no run's)
+        batch_core_rind(b, defect ? b->d_defect.get() : nullptr, thr, n_thr);
+        batch_download_core_rind(b, map, counts, stats);
+    })
+}
+
 // ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------
 // The resident HPvent, or the mask statistics and scalars, are no longer the last run's: the calls that
 // read a run's results refuse until the next one; an uploaded defect map and an enqueued CI stay.

@@ -32,6 +32,8 @@ public:
         int32_t dist_bins = 0;       // its n_bins (while distribution)
         bool heterogeneity = false;  // vh_batch_heterogeneity has been enqueued
         int32_t het_bins = 0;        // its n_bins (while heterogeneity)
+        bool core_rind = false;      // vh_batch_core_rind has been enqueued
+        int32_t cr_bands = 0;        // its n_thr + 1 (while core_rind)
         // an input, like the resident HPvent and mask: no transition but its own changes it
         bool proton = false;         // d_proton holds the batch's proton volumes
         bool proton_src = false;     // d_proton_src holds the proton on its own grid (vh_batch_upload_proton_src)
@@ -50,6 +52,7 @@ public:
     void montage_enqueued() { f_.montage = true; }
     void distribution_enqueued(int32_t bins) { f_.distribution = true; f_.dist_bins = bins; }
     void heterogeneity_enqueued(int32_t bins) { f_.heterogeneity = true; f_.het_bins = bins; }
+    void core_rind_enqueued(int32_t bands) { f_.core_rind = true; f_.cr_bands = bands; }
     void proton_uploaded() { f_.proton = true; }
     void proton_src_uploaded() { f_.proton_src = true; }
 
@@ -71,6 +74,9 @@ public:
     void need_heterogeneity() const {
         need(f_.heterogeneity, "vh_batch_heterogeneity has not been called since the last run");
     }
+    void need_core_rind() const {
+        need(f_.core_rind, "vh_batch_core_rind has not been called since the last run or the last edit of the inputs");
+    }
     void need_proton() const { need(f_.proton, "no proton resident: vh_batch_upload_proton first"); }
     void need_proton_src() const {
         need(f_.proton_src, "no proton source resident: vh_batch_upload_proton_src first");
@@ -89,6 +95,7 @@ public:
     double ci_minvox() const { return f_.ci_minvox; }
     int32_t dist_bins() const { return f_.dist_bins; }
     int32_t het_bins() const { return f_.het_bins; }
+    int32_t cr_bands() const { return f_.cr_bands; }
     const Fields &fields() const { return f_; }   // everything, read-only (tests/batch_state_check.cpp)
 
 private:
@@ -97,7 +104,7 @@ private:
     // replaced them (ran) or an edit of the resident inputs discarded them (forgot_run)
     void clear_derived() {
         f_.labels = f_.selection = f_.ci_fresh = false;
-        f_.layout = f_.overlay = f_.montage = f_.distribution = f_.heterogeneity = false;
+        f_.layout = f_.overlay = f_.montage = f_.distribution = f_.heterogeneity = f_.core_rind = false;
     }
     static void need(bool ok, const char *msg) { if (!ok) throw VhError{VH_ERR_ARG, msg}; }
 };

@@ -286,6 +286,11 @@ struct vh_batch {
     Buf<float> d_het;                // [nb][V] the last call's CoV maps
     Buf<uint32_t> d_het_hist;        // [nb][state.het_bins()] its histograms
     Buf<unsigned long long> d_het_stats;   // [nb][4] n_in, n_over, n_none, sum_fx
+    // vh_batch_core_rind (depth.hip): every buffer on first demand
+    Buf<uint16_t> d_cr_map;          // [nb][V] the last call's saturated D2 maps
+    Buf<uint16_t> d_cr_g;            // [nb][V] the column distances: scratch of the two kernels (bytes where R <= 510)
+    Buf<unsigned long long> d_cr_counts;   // [nb][state.cr_bands()][2] the band's voxels, its defect voxels
+    Buf<unsigned long long> d_cr_stats;    // [nb][2] n_mask, max D2
     // vh_batch_edit_mask / vh_batch_download_mask (mask_edit.hip): on first demand.  The edits' scratch
     // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
     Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
@@ -527,6 +532,15 @@ void vh_noise_sigma_launch(vh_batch *b, float *d_sigma);
 bool vh_het_takes(const vh_batch *b);
 void vh_het_launch(vh_batch *b, const float *src, const uint8_t *defect, float *map, uint32_t *d_hist,
                    unsigned long long *d_stats, int K, int min_count, int n_bins, float hi, float scale);
+// depth.hip: the saturated squared distance to the mask's edge of every study into map [nb][V], with the
+// band counts over thr [n_thr] (host) in d_counts [nb][n_thr + 1][2] and d_stats [nb][2] (both zeroed
+// here), the defect column from defect (nullable: 0); d_g [nb][V] is its scratch, the column distances;
+// vh_depth_takes: the grid fits; vh_depth_form: 0 when the shape's search runs on rows staged in LDS,
+// 1 when a row is too long for that and it reads g through the caches
+int vh_depth_form(int64_t R, int64_t C, int64_t Z);
+bool vh_depth_takes(const vh_batch *b);
+void vh_depth_launch(vh_batch *b, const uint8_t *defect, const uint16_t *thr, int n_thr, uint16_t *d_g, uint16_t *map,
+                     unsigned long long *d_counts, unsigned long long *d_stats);
 // mask_edit.hip: one disc dilation (erode 0) or erosion (erode 1) of every study, src -> dst (two
 // mask volumes of the batch), with d_radius [nb] in 0..5 (0: the study is copied);
 // vh_mask_edit_takes: the grid fits.  vh_mask_paint_launch: mask = paint(mask != 0, strokes != 0) in
