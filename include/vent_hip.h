@@ -49,6 +49,11 @@
  *                analysis: the exact squared in-plane distance of every mask voxel to the mask's edge,
  *                as a map, and the mask and defect voxels of every depth band, per study from the
  *                resident mask and defect map (build-defined); kernel-timing class "depth_b", not listed
+ *   vh_batch_components / vh_batch_download_components / vh_batch_filter_components / vh_components /
+ *                vh_filter_components  the connected components (4, 8, 6 or 26 neighbours) of the resident
+ *                defect map or mask: the canonical root and the size of every voxel's component, counts
+ *                per size class, and a filter by size and by rank (build-defined); kernel-timing class
+ *                "comp_b", not listed
  *   vh_batch_noise_sigma / vh_batch_denoise / vh_batch_download_hp / vh_noise_sigma / vh_denoise
  *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
  *                non-local-means filter of the resident HPvent, specified to the last bit, and the
@@ -490,6 +495,82 @@ int vh_core_rind(vh_ctx *ctx, const uint8_t *mask, const uint8_t *defect /* null
                  uint16_t *map, int64_t *counts, int64_t *stats);
 int vh_core_rind_form(int64_t R, int64_t C, int64_t Z);
 
+/* ---- the connected components of a device-resident batch ------------------------------------------
+ * How many defects there are, how large each one is, and a filter that drops the small ones or keeps
+ * the k largest -- of the resident defect map, or of the resident mask (the two lungs after
+ * vh_batch_segment).  Every output is an exact integer with one canonical value: no numbering of the
+ * labels is left to the implementation, and nothing depends on the order in which threads add
+ * (tests/components_ref.py is the same definition in numpy / scipy).
+ *
+ * One study is [R][C][Z], the slice axis fastest, V = R C Z.  The set: S = (a != 0) of one resident
+ * byte volume, source = VH_CC_DEFECT the resident defect map as it stands at the enqueue (the run's,
+ * vh_batch_set_defect's or vh_batch_select_defect's), VH_CC_MASK the resident mask.  A position
+ * outside the volume is not in S; nothing wraps around.
+ *
+ * The neighbourhood, conn:   4: |dr| + |dc| = 1, dz = 0          8: max(|dr|, |dc|) = 1, dz = 0
+ *                            6: |dr| + |dc| + |dz| = 1          26: max(|dr|, |dc|, |dz|) = 1
+ * With 4 and 8 voxels of different slices are never connected: every slice stands on its own, as in
+ * the other per-slice analyses.  A component is an equivalence class of S under the transitive closure
+ * of the neighbourhood.
+ *
+ * Per voxel: root int32 [R][C][Z], the smallest linear index (r C + c) Z + z over the voxels of its
+ * component, -1 off S: the canonical label.  size uint32 [R][C][Z], the number of voxels of its
+ * component, 0 off S.
+ *
+ * Per study: stats int64 [4] = n_set, n_comp, the size of the largest component (0: none) and that
+ * component's root (-1: none); among equal sizes the smaller root wins.  counts int64 [n_edges + 1][2]:
+ * edges holds n_edges (0..31) uint32 values 2 <= e[0] < e[1] < ...; a component's class is the number of
+ * edges <= its size; counts[k] = {components of class k, voxels in them}.  An empty S gives -1 / 0
+ * throughout.
+ *
+ * The filter: min_size uint32 [nb], each >= 1; keep_largest int32 [nb], 0..8, 0 = no limit (NULL: all
+ * 0).  A component's key is (size, -root), ordered lexicographically; its rank is the number of
+ * components of the study with a greater key.  A voxel of S is kept when its component has
+ * size >= min_size[q] and, where keep_largest[q] = k > 0, rank < k; every other voxel of the source is
+ * cleared; a kept voxel keeps its byte value.  kept int64 [nb][2] = {components kept, voxels kept}.
+ *
+ * vh_batch_components enqueues only (edges is read before it returns).  It reads its source and
+ * writes buffers of its own: nothing another call reads changes, so the CI stays fresh.  It may be
+ * called again; the download returns the last call's result, a snapshot like the core-rind's defect
+ * column: a later change of the source does not change it.  A new run, and whatever forgets the run,
+ * discards it.  vh_batch_download_components waits; every pointer is nullable.
+ *
+ * vh_batch_filter_components labels its source itself -- it does not depend on an earlier
+ * vh_batch_components, so it cannot apply stale sizes to a map that has changed since -- in the same
+ * device buffers: a download after it is VH_ERR_ARG until the next vh_batch_components.  With
+ * VH_CC_MASK it writes the resident mask and forgets the run, exactly as vh_batch_edit_mask does.  With
+ * VH_CC_DEFECT it writes the resident defect map, rebuilds the resident border from it (the 2-D
+ * calculateBorder of vh_border) and leaves the state vh_batch_set_defect leaves: the CI is no longer
+ * fresh, a selection is off, and vh_batch_download_defect's count is NOT updated -- it is the run's,
+ * as after vh_batch_set_defect; the filtered count is kept[q][1].  It enqueues only unless kept is
+ * given; then it waits.
+ *
+ * VH_ERR_ARG, with nothing enqueued: a null batch; source or conn out of range; n_edges outside 0..31;
+ * edges that are not strictly increasing or are below 2; a null min_size, a min_size of 0, a
+ * keep_largest outside 0..8; VH_CC_DEFECT with no defect maps resident (neither a run nor
+ * vh_batch_set_defect); a batch of more than 65535 studies; V >= 2^31 (no batch has one); a download
+ * without a vh_batch_components since the last run, forget or filter.  The kernel-timing class is
+ * "comp_b" (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * The kernels take every shape a batch accepts, in one form: a union-find whose parent array is the
+ * root map, tiles of 16 x 16 x min(Z, 24) voxels labelled in LDS and united across their faces; every
+ * device loop is bounded because an index strictly decreases along it.
+ *
+ * vh_components / vh_filter_components are the host-buffer forms on the context's scratch batch, for
+ * any byte volume a: no run behind them.  out (nullable) receives the filtered volume. */
+#define VH_CC_DEFECT 0
+#define VH_CC_MASK 1
+int vh_batch_components(vh_batch *b, int source, int conn, const uint32_t *edges, int32_t n_edges);   /* enqueue only */
+int vh_batch_download_components(vh_batch *b, int32_t *root /* [nb][R][C][Z] */, uint32_t *size /* [nb][R][C][Z] */,
+                                 int64_t *counts /* [nb][n_edges+1][2] */, int64_t *stats /* [nb][4] */);   /* waits; all nullable */
+int vh_batch_filter_components(vh_batch *b, int source, int conn, const uint32_t *min_size /* [nb] */,
+                               const int32_t *keep_largest /* [nb]; NULL = all 0 */,
+                               int64_t *kept /* [nb][2]; nullable; waits when given */);
+int vh_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
+                  const uint32_t *edges, int32_t n_edges, int32_t *root, uint32_t *size, int64_t *counts, int64_t *stats);
+int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
+                         const uint32_t *min_size, const int32_t *keep_largest, uint8_t *out, int64_t *kept);
+
 /* ---- the denoise option of a device-resident batch ("Denoise Option", Vent_Analysis.py:1025) -------
  * An in-plane non-local-means filter of the resident HPvent with a Tukey bisquare weight.  Every
  * operation is a correctly-rounded float32 add, subtract, multiply, divide or square root in a fixed
@@ -657,8 +738,10 @@ int vh_edit_mask(vh_ctx *ctx, const uint8_t *mask, int64_t R, int64_t C, int64_t
  * threshold of every study, and VH_ERR_EMPTY is returned (with thresh_out written, nothing else) when
  * that is NaN for one of them; mask_out, thresh_out and count are nullable.
  *
- * Not done here: connectivity across slices, component size filters, removal of the trachea, learned
- * segmentation. */
+ * Connectivity across slices and component size filters are vh_batch_components /
+ * vh_batch_filter_components (VH_CC_MASK, keep_largest = 2 keeps the two lungs and drops the specks and
+ * a trachea that does not touch them).  Not done here: the removal of a trachea that joins a lung,
+ * learned segmentation. */
 int vh_batch_upload_proton(vh_batch *b, const float *proton /* [nb][V] */);
 int vh_batch_proton_threshold(vh_batch *b, float *thresh /* [nb] */, float *pmax /* [nb], nullable */,
                               uint32_t *hist /* [nb][256], nullable */);

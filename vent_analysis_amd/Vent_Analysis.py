@@ -328,6 +328,60 @@ class Vent_Analysis:
                     thresholds=out['thresholds'], n_mask=int(out['stats'][0, 0]), d2=out['d2'][0],
                     depth_max_mm=px * float(np.sqrt(np.float64(out['stats'][0, 1]))))
 
+    def defect_components(self, conn=6, edges=(10, 100, 1000)):
+        """The connected components of ``defectArray`` as it stands (build-defined), on the GPU: how
+        many defects there are and how large each one is, under ``conn`` 4 | 8 (every slice on its
+        own) | 6 | 26 neighbours -- the spec is in include/vent_hip.h.  ``edges`` (voxel counts,
+        increasing, >= 2) separate the size classes.  Needs calculate_VDP first.  Returns a dict and
+        sets nothing on the object: ``root`` int32 [R][C][Z], the smallest linear index of the voxel's
+        defect (-1 off the defects), the defect's label; ``size`` uint32 [R][C][Z], its voxels;
+        ``n_defect_voxels``; ``n_components``; ``largest`` (voxels) and ``largest_root``; ``counts`` int64
+        [classes][2], the defects of each size class and their voxels; ``edges``; and from ``self.vox``
+        ``voxel_mL``, ``size_mL`` float64 [R][C][Z], ``largest_mL`` and ``class_mL`` float64 [classes]."""
+        if isinstance(self.defectArray, str):
+            raise ValueError("defect_components: defectArray is not set (run calculate_VDP first)")
+        _lib._components_args("defect", conn, edges)
+        out = _lib.components(np.asarray(self.defectArray) != 0, conn=conn, edges=edges, device=self.device)
+        ml = float(np.prod(np.divide(self.vox, 10)))
+        st = out['stats'][0]
+        return dict(root=out['root'][0], size=out['size'][0], n_defect_voxels=int(st[0]), n_components=int(st[1]),
+                    largest=int(st[2]), largest_root=int(st[3]), counts=out['counts'][0], edges=out['edges'],
+                    voxel_mL=ml, size_mL=out['size'][0] * ml, largest_mL=int(st[2]) * ml,
+                    class_mL=out['counts'][0][:, 1] * ml)
+
+    def filter_defects(self, min_size, conn=6):
+        """Drop the defects of fewer than ``min_size`` voxels from ``defectArray`` (build-defined), on
+        the GPU: the specks the linear-binning and k-means maps carry.  Components under ``conn`` 4 | 8
+        (every slice on its own) | 6 | 26 neighbours; a kept voxel keeps its value.  ``defectBorder`` is
+        recomputed from the filtered map (the 2-D calculateBorder); metadata and defectArrayLB are left
+        alone.  Needs calculate_VDP first.  Returns (defects kept, voxels kept)."""
+        if isinstance(self.defectArray, str):
+            raise ValueError("filter_defects: defectArray is not set (run calculate_VDP first)")
+        _lib._filter_components_args("defect", conn, min_size, 0, 1)
+        old = np.asarray(self.defectArray)
+        out, kept = _lib.filter_components(old != 0, conn=conn, min_size=min_size, device=self.device)
+        self.defectArray = old * (out[0] != 0)
+        self.defectBorder = _lib.border(out, device=self.device)[0] == 1
+        return int(kept[0, 0]), int(kept[0, 1])
+
+    def clean_mask(self, keep_largest=2, min_size=1, conn=6):
+        """Keep the ``keep_largest`` (1..8; 0: no limit) largest connected parts of ``self.mask`` that
+        have at least ``min_size`` voxels (build-defined), on the GPU: the two lungs after segment_mask,
+        without the trachea and the specks.  Components under ``conn`` 4 | 8 (every slice on its own) |
+        6 | 26 neighbours; among parts of one size the one that starts first stays.  A voxel counts as
+        set when it is nonzero; the result is stored in ``self.mask`` as 0/1 in the mask's dtype,
+        ``mask_border`` and ``metadata['LungVolume']`` are recomputed from it, and the new mask is
+        returned.  ``N4HPvent``, ``defectArray`` and the VDP entries of ``metadata`` are left as they are
+        and belong to the old mask until calculate_VDP is run again."""
+        _lib._filter_components_args("mask", conn, min_size, keep_largest, 1)
+        old = np.asarray(self.mask)
+        new, _ = _lib.filter_components(old != 0, conn=conn, min_size=min_size, keep_largest=keep_largest,
+                                        device=self.device)
+        self.mask = new[0].astype(old.dtype)
+        self.mask_border = self.calculateBorder(self.mask)
+        self.metadata['LungVolume'] = np.sum(self.mask == 1) * np.prod(np.divide(self.vox, 10)) / 1000
+        return self.mask
+
     def estimate_noise(self, A=None):
         """The noise sigma of ``A`` (default ``self.HPvent``) for denoise (build-defined): float32
         sqrt(sum(A^2) / (2 N)) over the voxels calculate_SNR counts as noise for ``self.mask`` -- the

@@ -389,6 +389,11 @@ _SIGS = {
     "vh_batch_download_core_rind": ([_P, _P, _P, _P], ct.c_int),
     "vh_core_rind_form": ([_I64, _I64, _I64], ct.c_int),
     "vh_core_rind": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, ct.c_int32, _P, _P, _P], ct.c_int),
+    "vh_batch_components": ([_P, ct.c_int, ct.c_int, _P, ct.c_int32], ct.c_int),
+    "vh_batch_download_components": ([_P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_filter_components": ([_P, ct.c_int, ct.c_int, _P, _P, _P], ct.c_int),
+    "vh_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, ct.c_int32, _P, _P, _P, _P], ct.c_int),
+    "vh_filter_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, _P, _P, _P], ct.c_int),
     "vh_batch_noise_sigma": ([_P, _P], ct.c_int),
     "vh_batch_denoise": ([_P, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int], ct.c_int),
     "vh_batch_download_hp": ([_P, _P], ct.c_int),
@@ -893,6 +898,93 @@ def core_rind(mask, defect=None, edges=(1.5, 3.5), device=0, thresholds=None):
     c.check(c.L.vh_core_rind(c.h, _ptr(m), _ptr(d), *m.shape[1:], B, _ptr(thr), thr.size,
                              _ptr(out), _ptr(counts), _ptr(stats)), "vh_core_rind")
     return dict(d2=out, counts=counts, stats=stats, thresholds=thr, band_vdp=band_vdp(counts))
+
+
+VH_CC_DEFECT, VH_CC_MASK = range(2)     # vh_batch_components sources
+_CC_SOURCES = {"defect": VH_CC_DEFECT, "mask": VH_CC_MASK}
+CC_CONNS = (4, 8, 6, 26)
+
+
+def _cc_conn(conn):
+    """4 | 8 (per slice) | 6 | 26 -> the int; anything else raises ValueError."""
+    if isinstance(conn, (bool, float)) or not isinstance(conn, (int, np.integer)) or int(conn) not in CC_CONNS:
+        raise ValueError(f"components: conn is one of 4, 8, 6, 26, got {conn!r}")
+    return int(conn)
+
+
+def _components_args(source, conn, edges):
+    """(source int, conn int, edges uint32 contiguous) for vh_batch_components: ``source`` 'defect' |
+    'mask' or the VH_CC_* ints; ``conn`` 4 | 8 | 6 | 26; ``edges`` at most 31 ints, 2 <= e[0] < e[1] <
+    ... < 2^32.  ValueError for what the library would refuse, so the message names the argument."""
+    source = _named_int(source, _CC_SOURCES, "components source")
+    conn = _cc_conn(conn)
+    e = np.asarray(edges)
+    if e.size == 0:
+        return source, conn, np.zeros(0, np.uint32)
+    if e.ndim != 1 or e.dtype == np.bool_ or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"components: edges is a sequence of ints, got {edges!r}")
+    if e.size > 31:
+        raise ValueError(f"components: at most 31 edges, got {e.size}")
+    e = e.astype(np.int64) if e.dtype != np.uint64 else e
+    if e[0] < 2 or e[-1] >= 2 ** 32 or (np.diff(e.astype(np.float64)) <= 0).any():
+        raise ValueError(f"components: edges must be strictly increasing in 2..2^32 - 1, got {e.tolist()}")
+    return source, conn, np.ascontiguousarray(e, dtype=np.uint32)
+
+
+def _per_study_ints(v, n, lo, hi, dtype, what):
+    """A scalar or one int per study -> ``dtype`` [n] contiguous, every value in lo..hi; else ValueError."""
+    a = np.asarray(v)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"filter_components: {what} is an int or one int per study, got {v!r}")
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+        raise ValueError(f"filter_components: {n} studies, got {what} of shape {a.shape}")
+    if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+        raise ValueError(f"filter_components: every {what} must be {lo}..{hi}, got {v!r}")
+    return np.ascontiguousarray(np.broadcast_to(a, (n,)), dtype=dtype)
+
+
+def _filter_components_args(source, conn, min_size, keep_largest, n):
+    """(source int, conn int, min_size uint32 [n], keep_largest int32 [n]) for
+    vh_batch_filter_components: ``min_size`` >= 1 and ``keep_largest`` 0..8 (0: no limit), each a scalar
+    or one int per study.  ValueError for what the library would refuse."""
+    source = _named_int(source, _CC_SOURCES, "components source")
+    conn = _cc_conn(conn)
+    return (source, conn, _per_study_ints(min_size, n, 1, 2 ** 32 - 1, np.uint32, "min_size"),
+            _per_study_ints(keep_largest, n, 0, 8, np.int32, "keep_largest"))
+
+
+def components(a, conn=6, edges=(), device=0):
+    """The connected components of byte volumes on the host (vh_components; the spec is in
+    include/vent_hip.h): ``a`` a 3-D volume or a 4-D batch of any dtype, nonzero counting as set.  No
+    run behind it.  Returns the dict of Batch.download_components."""
+    _, conn, e = _components_args(VH_CC_MASK, conn, edges)
+    m = as_batch(_mask_u8(a), np.uint8)
+    c = context(device)
+    B = m.shape[0]
+    root = np.empty(m.shape, np.int32)
+    size = np.empty(m.shape, np.uint32)
+    counts = np.zeros((B, e.size + 1, 2), np.int64)
+    stats = np.zeros((B, 4), np.int64)
+    c.check(c.L.vh_components(c.h, _ptr(m), *m.shape[1:], B, conn, _ptr(e), e.size, _ptr(root), _ptr(size),
+                              _ptr(counts), _ptr(stats)), "vh_components")
+    return dict(root=root, size=size, counts=counts, stats=stats, edges=e)
+
+
+def filter_components(a, conn=6, min_size=1, keep_largest=0, device=0):
+    """The component filter on the host (vh_filter_components): ``a`` as for components(); a component
+    stays when it has ``min_size`` voxels and, with ``keep_largest`` = k > 0, is among the k largest
+    (ties: the smaller root first); each a scalar or one int per study.  Returns (out, kept): uint8
+    [B][R][C][Z], the kept voxels with their byte values (1 where ``a`` is not uint8), and int64 [B][2]
+    = components kept, voxels kept."""
+    m = as_batch(_mask_u8(a), np.uint8)
+    B = m.shape[0]
+    _, conn, ms, kl = _filter_components_args(VH_CC_MASK, conn, min_size, keep_largest, B)
+    c = context(device)
+    out = np.empty_like(m)
+    kept = np.zeros((B, 2), np.int64)
+    c.check(c.L.vh_filter_components(c.h, _ptr(m), *m.shape[1:], B, conn, _ptr(ms), _ptr(kl), _ptr(out),
+                                     _ptr(kept)), "vh_filter_components")
+    return out, kept
 
 
 def _denoise_args(sigma, n, strength, search, patch):
@@ -1410,6 +1502,47 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_core_rind(self.h, _ptr(out), _ptr(counts), _ptr(stats)),
                        "vh_batch_download_core_rind")
         return dict(d2=out, counts=counts, stats=stats, thresholds=thr.copy(), band_vdp=band_vdp(counts))
+
+    def components(self, source="defect", conn=6, edges=()):
+        """Enqueue the connected components of every study (vh_batch_components; the spec is in
+        include/vent_hip.h): of the resident defect map as it stands (``source`` 'defect': needs a run
+        or upload_defect) or of the resident mask ('mask'), under ``conn`` 4 | 8 (every slice on its
+        own) | 6 | 26 neighbours.  ``edges`` (ints, increasing, >= 2) separate the size classes of the
+        counts.  Read-only; download_components fetches the last call's result."""
+        source, conn, e = _components_args(source, conn, edges)
+        self.ctx.check(self.L.vh_batch_components(self.h, source, conn, _ptr(e), e.size), "vh_batch_components")
+        self._cc = e
+
+    def download_components(self, root=True, size=True):
+        """The last components() as a dict: ``root`` int32 [B][R][C][Z], the smallest linear index of
+        the voxel's component, -1 off the set; ``size`` uint32 [B][R][C][Z], the component's voxels, 0
+        off the set (each None when not asked for: only the summary comes back); ``counts`` int64
+        [B][classes][2], the components of each size class and their voxels; ``stats`` int64 [B][4] =
+        n_set, n_comp, the largest component's size (0: none) and root (-1: none); ``edges`` uint32."""
+        e = getattr(self, "_cc", np.zeros(0, np.uint32))
+        B = self.shape[0]
+        r = np.empty(self.shape, np.int32) if root else None
+        sz = np.empty(self.shape, np.uint32) if size else None
+        counts = np.zeros((B, e.size + 1, 2), np.int64)
+        stats = np.zeros((B, 4), np.int64)
+        self.ctx.check(self.L.vh_batch_download_components(self.h, _ptr(r), _ptr(sz), _ptr(counts), _ptr(stats)),
+                       "vh_batch_download_components")
+        return dict(root=r, size=sz, counts=counts, stats=stats, edges=e.copy())
+
+    def filter_components(self, source="defect", conn=6, min_size=1, keep_largest=0):
+        """Clear the small components of the resident defect map or mask (vh_batch_filter_components):
+        a component stays when it has ``min_size`` voxels and, with ``keep_largest`` = k in 1..8, is among
+        the k largest of its study (ties: the smaller root first); each a scalar or one int per study.
+        'mask' puts the batch back where upload() left it, like edit_mask; 'defect' rebuilds the
+        resident border and leaves the batch as upload_defect does (download_defect's count stays the
+        run's).  A components() result is discarded.  Returns ``kept`` int64 [B][2] = components kept,
+        voxels kept; waits."""
+        B = self.shape[0]
+        source, conn, ms, kl = _filter_components_args(source, conn, min_size, keep_largest, B)
+        kept = np.zeros((B, 2), np.int64)
+        self.ctx.check(self.L.vh_batch_filter_components(self.h, source, conn, _ptr(ms), _ptr(kl), _ptr(kept)),
+                       "vh_batch_filter_components")
+        return kept
 
     def noise_sigma(self):
         """float32 [B]: the noise of each resident HPvent (vh_batch_noise_sigma), sqrt(S2 / (2 N))

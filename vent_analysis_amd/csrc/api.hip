@@ -1286,6 +1286,161 @@ int vh_core_rind(vh_ctx *ctx, const uint8_t *mask, const uint8_t *defect, int64_
     })
 }
 
+// ---- the connected components of a device-resident batch (components.hip) --------------------------
+// the argument checks (host only: nothing is enqueued before they pass)
+static void check_cc(int source, int conn) {
+    if (source != VH_CC_DEFECT && source != VH_CC_MASK) throw VhError{VH_ERR_ARG, "source must be VH_CC_DEFECT or VH_CC_MASK"};
+    if (conn != 4 && conn != 8 && conn != 6 && conn != 26) throw VhError{VH_ERR_ARG, "conn must be 4, 8, 6 or 26"};
+}
+
+static void check_cc_edges(const uint32_t *edges, int32_t n_edges) {
+    if (n_edges < 0 || n_edges > 31) throw VhError{VH_ERR_ARG, "n_edges must be 0..31"};
+    if (n_edges > 0 && !edges) throw VhError{VH_ERR_ARG, "null edges"};
+    for (int32_t i = 0; i < n_edges; ++i)
+        if (edges[i] < 2 || (i > 0 && edges[i] <= edges[i - 1]))
+            throw VhError{VH_ERR_ARG, "edges must be strictly increasing and >= 2"};
+}
+
+static void check_cc_filter(const uint32_t *min_size, const int32_t *keep_largest, int64_t nb) {
+    if (!min_size) throw VhError{VH_ERR_ARG, "null min_size"};
+    for (int64_t i = 0; i < nb; ++i) {
+        if (min_size[i] < 1) throw VhError{VH_ERR_ARG, "every min_size must be >= 1 (study " + std::to_string(i) + ")"};
+        if (keep_largest && (keep_largest[i] < 0 || keep_largest[i] > 8))
+            throw VhError{VH_ERR_ARG, "every keep_largest must be 0..8 (study " + std::to_string(i) + ")"};
+    }
+}
+
+// the state's check of the source and the volume it names
+static uint8_t *cc_source(vh_batch *b, int source) {
+    if (source == VH_CC_DEFECT) b->state.need_defect();
+    if (!vh_cc_takes(b)) throw VhError{VH_ERR_ARG, "components: more than 65535 studies or a volume of 2^31 voxels"};
+    return source == VH_CC_DEFECT ? b->d_defect.get() : b->d_mask.get();
+}
+
+// Enqueue the labelling of src.  It writes its own buffers only, so nothing another call on the batch
+// reads changes (the CI stays fresh).
+static void batch_cc_label(vh_batch *b, const uint8_t *src, int conn, const uint32_t *edges, int32_t n_edges) {
+    b->d_cc_root.reserve((size_t)b->nb * b->V);
+    b->d_cc_size.reserve((size_t)b->nb * b->V);
+    b->d_cc_counts.reserve((size_t)b->nb * 64);   // the largest n_edges: no regrowth
+    b->d_cc_stats.reserve((size_t)b->nb * 4);
+    vh_cc_launch(b, src, conn, edges, n_edges, b->d_cc_root, b->d_cc_size, b->d_cc_counts, b->d_cc_stats);
+}
+
+static void batch_components(vh_batch *b, int source, int conn, const uint32_t *edges, int32_t n_edges) {
+    batch_cc_label(b, cc_source(b, source), conn, edges, n_edges);
+    b->state.components_enqueued(n_edges + 1);
+}
+
+// stats leaves the device as n_set, n_comp, the largest key, 0: the key becomes the size and the root here
+static void batch_download_components(vh_batch *b, int32_t *root, uint32_t *size, int64_t *counts, int64_t *stats) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (root) HIP_TRY(hipMemcpyAsync(root, b->d_cc_root, sizeof(int32_t) * nb * b->V, hipMemcpyDeviceToHost, st));
+    if (size) HIP_TRY(hipMemcpyAsync(size, b->d_cc_size, sizeof(uint32_t) * nb * b->V, hipMemcpyDeviceToHost, st));
+    if (counts)
+        HIP_TRY(hipMemcpyAsync(counts, b->d_cc_counts, sizeof(int64_t) * nb * 2 * b->state.cc_classes(),
+                               hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, b->d_cc_stats, sizeof(int64_t) * nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stats)
+        for (size_t q = 0; q < nb; ++q) {
+            const uint64_t key = (uint64_t)stats[4 * q + 2];
+            stats[4 * q + 2] = (int64_t)(key >> 32);
+            stats[4 * q + 3] = key ? (int64_t)(int32_t)~(uint32_t)(key & 0xffffffffu) : -1;
+        }
+}
+
+// Enqueue the filter: the labelling of the source as it stands, the picks, the pass that clears; then
+// what a change of that source entails.  kept (nullable) waits.
+static void batch_filter_components(vh_batch *b, int source, int conn, const uint32_t *min_size,
+                                    const int32_t *keep_largest, int64_t *kept) {
+    uint8_t *src = cc_source(b, source);
+    const size_t nb = (size_t)b->nb;
+    const std::vector<int32_t> none(keep_largest ? 0 : nb, 0);
+    const int32_t *keep = keep_largest ? keep_largest : none.data();
+    const int kmax = *std::max_element(keep, keep + nb);
+    b->d_cc_min.reserve(nb);
+    b->d_cc_keep.reserve(nb);
+    b->d_cc_picks.reserve(nb * 8);
+    b->d_cc_kept.reserve(nb * 2);
+    b->state.components_filtered();   // (the buffers are relabelled, whatever follows)
+    // (pageable sources: the copies have left min_size and keep when the calls return)
+    HIP_TRY(hipMemcpyAsync(b->d_cc_min, min_size, sizeof(uint32_t) * nb, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->d_cc_keep, keep, sizeof(int32_t) * nb, hipMemcpyHostToDevice, b->stream));
+    batch_cc_label(b, src, conn, nullptr, 0);
+    if (source == VH_CC_DEFECT)
+        b->state.defect_replaced();
+    else
+        b->state.forgot_run();
+    vh_cc_filter_launch(b, src, b->d_cc_root, b->d_cc_size, b->d_cc_min, b->d_cc_keep, kmax, b->d_cc_picks, b->d_cc_kept);
+    if (source == VH_CC_DEFECT) vh_launch_border(b, b->d_defect, b->d_border);
+    if (kept) d2h_on_stream(b, kept, b->d_cc_kept, sizeof(int64_t) * nb * 2);
+}
+
+int vh_batch_components(vh_batch *b, int source, int conn, const uint32_t *edges, int32_t n_edges) {
+    BATCH_TRY(b, {
+        check_cc(source, conn);
+        check_cc_edges(edges, n_edges);
+        batch_components(b, source, conn, edges, n_edges);
+    })
+}
+
+int vh_batch_download_components(vh_batch *b, int32_t *root, uint32_t *size, int64_t *counts, int64_t *stats) {
+    BATCH_TRY(b, {
+        b->state.need_components();
+        batch_download_components(b, root, size, counts, stats);
+    })
+}
+
+int vh_batch_filter_components(vh_batch *b, int source, int conn, const uint32_t *min_size,
+                               const int32_t *keep_largest, int64_t *kept) {
+    BATCH_TRY(b, {
+        check_cc(source, conn);
+        check_cc_filter(min_size, keep_largest, b->nb);
+        batch_filter_components(b, source, conn, min_size, keep_largest, kept);
+    })
+}
+
+int vh_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
+                  const uint32_t *edges, int32_t n_edges, int32_t *root, uint32_t *size, int64_t *counts,
+                  int64_t *stats) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!a) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_cc(VH_CC_MASK, conn);
+        check_cc_edges(edges, n_edges);
+        check_dims(R, C, Z, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, nullptr, a);   // (the volume rides in the scratch batch's mask)
+        b->state.forgot_run();         // (the scratch batch's volumes are no run's)
+        batch_components(b, VH_CC_MASK, conn, edges, n_edges);
+        batch_download_components(b, root, size, counts, stats);
+    })
+}
+
+int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
+                         const uint32_t *min_size, const int32_t *keep_largest, uint8_t *out, int64_t *kept) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!a) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_cc(VH_CC_MASK, conn);
+        check_dims(R, C, Z, batch);
+        check_cc_filter(min_size, keep_largest, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, nullptr, a);
+        batch_filter_components(b, VH_CC_MASK, conn, min_size, keep_largest, nullptr);
+        if (kept) HIP_TRY(hipMemcpyAsync(kept, b->d_cc_kept, sizeof(int64_t) * (size_t)batch * 2, hipMemcpyDeviceToHost, b->stream));
+        if (out) HIP_TRY(hipMemcpyAsync(out, b->d_mask, (size_t)batch * b->V, hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    })
+}
+
 // ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------
 // The resident HPvent, or the mask statistics and scalars, are no longer the last run's: the calls that
 // read a run's results refuse until the next one; an uploaded defect map and an enqueued CI stay.

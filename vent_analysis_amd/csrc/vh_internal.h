@@ -291,6 +291,15 @@ struct vh_batch {
     Buf<uint16_t> d_cr_g;            // [nb][V] the column distances: scratch of the two kernels (bytes where R <= 510)
     Buf<unsigned long long> d_cr_counts;   // [nb][state.cr_bands()][2] the band's voxels, its defect voxels
     Buf<unsigned long long> d_cr_stats;    // [nb][2] n_mask, max D2
+    // vh_batch_components / vh_batch_filter_components (components.hip): every buffer on first demand
+    Buf<int32_t> d_cc_root;          // [nb][V] the last labelling's roots: the union-find's parent array
+    Buf<uint32_t> d_cc_size;         // [nb][V] its component sizes
+    Buf<unsigned long long> d_cc_counts;   // [nb][state.cc_classes()][2] the class's components, their voxels
+    Buf<unsigned long long> d_cc_stats;    // [nb][4] n_set, n_comp, the largest key (size << 32 | ~root), unused
+    Buf<uint32_t> d_cc_min;          // [nb] the last filter's min_size
+    Buf<int32_t> d_cc_keep;          // [nb] its keep_largest
+    Buf<unsigned long long> d_cc_picks;    // [nb][8] its picks: the k largest keys of each study, in order
+    Buf<unsigned long long> d_cc_kept;     // [nb][2] the components and the voxels it kept
     // vh_batch_edit_mask / vh_batch_download_mask (mask_edit.hip): on first demand.  The edits' scratch
     // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
     Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
@@ -541,6 +550,18 @@ int vh_depth_form(int64_t R, int64_t C, int64_t Z);
 bool vh_depth_takes(const vh_batch *b);
 void vh_depth_launch(vh_batch *b, const uint8_t *defect, const uint16_t *thr, int n_thr, uint16_t *d_g, uint16_t *map,
                      unsigned long long *d_counts, unsigned long long *d_stats);
+// components.hip: the connected components of src [nb][V] (nonzero: set) under conn (4, 8, 6, 26): the
+// roots and sizes into root / size [nb][V], the class counts over edges [n_edges] (host) into d_counts
+// [nb][n_edges + 1][2] and the summary into d_stats [nb][4] = n_set, n_comp, the largest component's key
+// size << 32 | ~root (0: none), unused (both zeroed here).  vh_cc_filter_launch: clears in src the voxels
+// whose component (root / size of a labelling of src as it stands) is below d_min [nb] voxels or, where
+// d_keep [nb] = k > 0, not among the k largest; kmax = the largest d_keep (<= 8); d_picks [nb][8] is its
+// scratch, d_kept [nb][2] = components, voxels kept (both zeroed here).  vh_cc_takes: the grid fits
+bool vh_cc_takes(const vh_batch *b);
+void vh_cc_launch(vh_batch *b, const uint8_t *src, int conn, const uint32_t *edges, int n_edges, int *root,
+                  uint32_t *size, unsigned long long *d_counts, unsigned long long *d_stats);
+void vh_cc_filter_launch(vh_batch *b, uint8_t *src, const int *root, const uint32_t *size, const uint32_t *d_min,
+                         const int32_t *d_keep, int kmax, unsigned long long *d_picks, unsigned long long *d_kept);
 // mask_edit.hip: one disc dilation (erode 0) or erosion (erode 1) of every study, src -> dst (two
 // mask volumes of the batch), with d_radius [nb] in 0..5 (0: the study is copied);
 // vh_mask_edit_takes: the grid fits.  vh_mask_paint_launch: mask = paint(mask != 0, strokes != 0) in
