@@ -108,6 +108,7 @@ struct StudyMisc {
     float bin_min, slope, bmax, pad;
 #ifdef ST_PROF
     unsigned long long fprof[4];   // wave of thread st_pt: fit rows / push / contract / items
+    unsigned long long eprof[9];   // thread st_pt: emap set-up, then slot / pointwise pass in turn
 #endif
     double sd, sd2, conv;
     ChainState ch;             // PC's result (conv of the last iteration)
@@ -795,6 +796,18 @@ __device__ __forceinline__ void hist_slice(const float *Ub, int64_t j_begin, int
     __syncthreads();
 }
 
+// The Wiener kernel's Gaussian at point i of the padded series.  A function of its own, not inlined:
+// inlined, the double exp's polynomial constants became invariants of the kernel's iteration loop,
+// lived in spill slots and were reloaded one at a time, each behind its own wait, inside the Horner
+// chain of every call (twice on the waves that hold point 0 or P / 2).
+__device__ __noinline__ double emap_kernel_point(int i, float sf, float ef) {
+    const int P = VH_FFT_P;
+    if (i == 0) return (double)sf;
+    if (i == P / 2) return (double)sf * exp(-0.25 * (double)((float)P * (float)P) * (double)ef);
+    const float nf = (float)(i < P / 2 ? i : P - i);
+    return (double)(sf * expf_cr_tail(-(nf * nf) * ef));
+}
+
 // emap (S4; same arithmetic as n4.hip k_n4_emap and the oracle): E(u) of the bins into sE.
 // series(h): the 64-bit S3 sum of bin h (24 fraction bits).  Only the five FFT calls run on one or
 // two waves; the pointwise passes between them (Wiener filter, clamp / moment series, kernel
@@ -803,8 +816,22 @@ __device__ __forceinline__ void hist_slice(const float *Ub, int64_t j_begin, int
 // round 5).
 template <class Series>
 __device__ __forceinline__ void emap_phase(const StudyArgs &a, const EmapW &w, float *sE, float bmin, float slope,
-                                           const Series &series) {
-    const int t = threadIdx.x, wv = t >> 6;
+                                           const Series &series, unsigned long long *eprof = nullptr) {
+    // (the thread index as a value made here: the passes' LDS addresses are computed where they are
+    // used, not kept through the kernel in spill slots)
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int wv = t >> 6;
+    // eprof (profiling builds): thread 0 adds the cycles of the set-up, of each transform slot and
+    // of each pointwise pass, every one up to and with its barrier
+    unsigned long long epc = eprof ? clock64() : 0ull;
+    const auto emark = [&](int k) {
+        if (eprof && t == 0) {
+            const unsigned long long c = clock64();
+            eprof[k] += c - epc;
+            epc = c;
+        }
+    };
     double2 *const V = w.V, *const F = w.F, *const DEN = w.DEN, *const TW = w.TW;
     const int P = VH_FFT_P, bins = a.bins, off = (P - bins) / 2;
     const float sFWHM = a.fwhm / slope;
@@ -816,30 +843,29 @@ __device__ __forceinline__ void emap_phase(const StudyArgs &a, const EmapW &w, f
         const int h = i - off;
         const unsigned long long s = h >= 0 && h < bins ? series(h) : 0ull;
         V[fpad(i)] = make_double2((double)s * (1.0 / 16777216.0), 0.0);
-        double fx;
-        if (i == 0) {
-            fx = (double)sf;
-        } else if (i == P / 2) {
-            fx = (double)sf * exp(-0.25 * (double)((float)P * (float)P) * (double)ef);
-        } else {
-            const float nf = (float)(i < P / 2 ? i : P - i);
-            fx = (double)(sf * expf_cr_tail(-(nf * nf) * ef));
-        }
-        F[fpad(i)] = make_double2(fx, 0.0);
+        F[fpad(i)] = make_double2(emap_kernel_point(i, sf, ef), 0.0);
     }
     if (t < P / 2) TW[t] = twv;
     __syncthreads();
+    emark(0);
     if (wv < 2) wave_fft_lds(wv ? F : V, TW, false, FftId(), FftId());
     __syncthreads();
+    emark(1);
+    // (the noise as a double made here: converted once for the kernel it sat in a register pair that
+    // the transforms' pass loops borrowed and reloaded from its spill slot at the end of every pass)
+    float noise = a.noise;
+    asm volatile("" : "+v"(noise));
     for (int i = t; i < P; i += ST_TPB) {   // Wiener filter
         const double2 f = F[fpad(i)], v = V[fpad(i)];
         const double fa = f.x, fb = f.y;
-        const double gg = fa / ((fa * fa - (-fb) * fb) + (double)a.noise);
+        const double gg = fa / ((fa * fa - (-fb) * fb) + (double)noise);
         V[fpad(i)] = make_double2(v.x * gg, v.y * gg);
     }
     __syncthreads();
+    emark(2);
     if (wv == 0) wave_fft_lds(V, TW, true, FftId(), FftId());   // inverse
     __syncthreads();
+    emark(3);
     for (int i = t; i < P; i += ST_TPB) {   // clamp; the moment series' points
         const double2 v = V[fpad(i)];
         const double ur = v.x > 0.0 ? v.x : 0.0;
@@ -848,9 +874,11 @@ __device__ __forceinline__ void emap_phase(const StudyArgs &a, const EmapW &w, f
         V[fpad(i)] = make_double2((double)c * ur, 0.0);
     }
     __syncthreads();
+    emark(4);
     // each series: forward, times the kernel's transform, inverse
     if (wv < 2) wave_fft_lds(wv ? DEN : V, TW, false, FftId(), FftId());
     __syncthreads();
+    emark(5);
     for (int e = t; e < 2 * P; e += ST_TPB) {
         double2 *const x = e < P ? V : DEN;
         const int i = e < P ? e : e - P;
@@ -859,13 +887,16 @@ __device__ __forceinline__ void emap_phase(const StudyArgs &a, const EmapW &w, f
         x[fpad(i)] = make_double2(v.x * fa - v.y * fb, v.x * fb + v.y * fa);
     }
     __syncthreads();
+    emark(6);
     if (wv < 2) wave_fft_lds(wv ? DEN : V, TW, true, FftId(), FftId());
     __syncthreads();
+    emark(7);
     for (int i = t; i < bins; i += ST_TPB) {
         const double d = DEN[fpad(i + off)].x;
         sE[i] = d != 0.0 ? (float)(V[fpad(i + off)].x / d) : 0.0f;
     }
     __syncthreads();
+    emark(8);
 }
 
 // lat (S6): lattice += phi = num / den of every control point (no barrier)
@@ -1036,6 +1067,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
     unsigned long long st_prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = clock64();
     int st_nfirst = 0, st_nother = 0;   // evals of a level's first iteration (levels > 0) / all others
     if (t == 0) M.fprof[0] = M.fprof[1] = M.fprof[2] = M.fprof[3] = 0ull;
+    if (t < 9) M.eprof[t] = 0ull;
 #endif
     int tpar = 0;   // Tg buffer of the last computed field's T windows
     for (int L = 0; L < a.nlev; ++L) {
@@ -1072,7 +1104,11 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
                     if (h > 0) s += hist_osum(EW.Hc[q * VH_MAX_BINS + h - 1]);
                 }
                 return s;
+#ifdef ST_PROF
+            }, M.eprof);
+#else
             });
+#endif
             ST_MARK(3);
 #ifdef ST_PROF
             fit_pass<0>(a, b, M, next, W, Ub, n, sE, bmin, rinv, ring, numfix, wv == (st_pt >> 6) ? M.fprof : nullptr);
@@ -1161,6 +1197,9 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
                st_prof[4], st_prof[5], st_prof[6] + st_prof[11], st_prof[7], st_prof[8], st_prof[9], st_prof[10]);
         printf("ST_PROF fit: rows %llu push %llu contract %llu items %llu\n", M.fprof[0], M.fprof[1],
                M.fprof[2], M.fprof[3]);
+        printf("ST_PROF emap: setup %llu fwdVF %llu wiener %llu invV %llu clamp %llu fwdVD %llu product %llu "
+               "invVD %llu divide %llu\n", M.eprof[0], M.eprof[1], M.eprof[2], M.eprof[3], M.eprof[4],
+               M.eprof[5], M.eprof[6], M.eprof[7], M.eprof[8]);
         // (the eval figure above is the sum of the two below)
         printf("ST_PROF eval: first-of-level %llu in %d other %llu in %d\n", st_prof[11], st_nfirst,
                st_prof[6], st_nother);
