@@ -54,6 +54,11 @@
  *                defect map or mask: the canonical root and the size of every voxel's component, counts
  *                per size class, and a filter by size and by rank (build-defined); kernel-timing class
  *                "comp_b", not listed
+ *   vh_batch_zones / vh_batch_download_zones / vh_zones / vh_zone_parts / vh_zone_split  the regional
+ *                analysis: a zone map (left / right lung, thirds, a grid of parts, or the caller's label
+ *                volume) and per zone the mask, defect and linear-binning class counts and the histogram
+ *                of the normalised signal, per study from the resident buffers (build-defined);
+ *                kernel-timing class "zones_b", not listed
  *   vh_batch_noise_sigma / vh_batch_denoise / vh_batch_download_hp / vh_noise_sigma / vh_denoise
  *                the "Denoise Option" of the reference's list (Vent_Analysis.py:1025): an in-plane
  *                non-local-means filter of the resident HPvent, specified to the last bit, and the
@@ -570,6 +575,91 @@ int vh_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z
                   const uint32_t *edges, int32_t n_edges, int32_t *root, uint32_t *size, int64_t *counts, int64_t *stats);
 int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
                          const uint32_t *min_size, const int32_t *keep_largest, uint8_t *out, int64_t *kept);
+
+/* ---- the regional analysis of a device-resident batch ----------------------------------------------
+ * Where in the lung the defects lie: the VDP, the class counts and the signal histogram of the left and
+ * the right lung, of the upper, middle and lower third, of a grid of parts, or of the zones of a
+ * caller's own label volume (lobes from a registered CT).  Every output is an integer, so the result
+ * does not depend on the order in which threads add (tests/zones_ref.py is the same definition in
+ * numpy; vent_analysis_amd/csrc/zones_host.h is the rule the kernels and the two host functions share).
+ *
+ * One study is [R][C][Z], the slice axis fastest, V = R C Z.  A voxel is "on" when mask != 0.  Pr[r],
+ * Pc[c], Pz[z] are the on voxels of row r, column c and slice z of the study.
+ *
+ * The bounds of an axis: lo and hi, the first and the last index with P > 0, w = hi - lo + 1.  An empty
+ * mask has lo = 0, hi = -1 on every axis and every part index 0.
+ *
+ * The parts of an axis into p parts (1..32), for every index i of the axis:
+ *   by = VH_ZONE_EXTENT  part(i) = clamp(floor((i - lo) p / w), 0, p - 1); indices below lo are in part 0
+ *   by = VH_ZONE_COUNT   part(i) = min(p - 1, floor(cum(i) p / total)), cum(i) the sum of P[j] over j < i,
+ *                        total the sum of P, in 64-bit integers
+ * A part may be empty (p > w, or a plane that holds more than total / p voxels).
+ *
+ * The lateral split (left and right lung): among the columns lo_c + w_c / 4 .. hi_c - w_c / 4 (integer
+ * division: the whole interval where w_c < 4) s is the one with the smallest Pc, the smallest such
+ * column on a tie; the side of column c is 0 for c < s and 1 for c >= s.  An empty mask has s = 0.
+ *
+ * The zone of an on voxel: 1 + (part_r nc + col) pz + part_z with parts = {pr, pc, pz}; with lateral
+ * nc = 2, col = the side and pc must be 1; without it nc = pc and col = part_c.  K = pr nc pz <= 32.
+ * The zone byte of a voxel off the mask is 0.
+ *
+ * labels != NULL, the caller's zones: K = n_zones (1..32); labels [nb][V] is copied to the device before
+ * the call returns; a byte l in 1..K on an on voxel is zone l, any other byte on an on voxel zone 0,
+ * "unassigned"; parts, lateral and by are ignored.  The resident zone map is what was used: the zone
+ * byte on on voxels, 0 elsewhere.
+ *
+ * Per study and zone k = 0..K, over the on voxels of the zone, from the N4 volume the last run's chain
+ * read, the resident defect map as it stands at the enqueue, and the run's LB classes:
+ *   counts int64 [K + 1][VH_ZONE_COLS]  the voxels, those with defect != 0, those of LB class 1..6
+ *   hist uint32 [K + 1][n_bins], stats int64 [K + 1][4] = n_in, n_below, n_over, sum_fx
+ * by the distribution's rule: nv = float32(x / d), d the run's mean_anchor (VH_NORM_MEAN) or p99
+ * (VH_NORM_P99); for 0 <= nv < hi the bin is min(n_bins - 1, (int)float32(nv * scale)) with
+ * scale = (float)n_bins / hi formed once in float32, it counts in n_in, and sum_fx +=
+ * (int64)float32(nv * 16777216.0f), the heterogeneity's fixed point: the zone's mean normalised signal
+ * is sum_fx / 2^24 / n_in.  nv < 0 counts in n_below; everything else (>= hi, NaN, a zero divisor) in
+ * n_over.
+ *   geom int32 [8] = lo_r, hi_r, lo_c, hi_c, lo_z, hi_z, s, 0 (s = -1 without lateral and with labels;
+ *   with labels the bounds are still the mask's)
+ *
+ * vh_batch_zones enqueues only, without a host wait (with labels it returns once their copy has left
+ * the caller's buffer).  It needs a run, reads what the run and the other calls left and writes buffers
+ * of its own: nothing another call reads changes, so the CI stays fresh.  It may be called again: the
+ * download returns the last call's result; a new run, and whatever forgets the run, discards it.
+ * VH_ERR_ARG, with nothing enqueued: a null batch; no run; norm not VH_NORM_*; n_bins outside 1..256; hi
+ * not finite, <= 0 or > 64 (the bound keeps sum_fx inside int64 at V < 2^31); without labels: by not
+ * VH_ZONE_*, null parts, a part count below 1, K > 32, lateral outside {0, 1}, lateral with
+ * parts[1] != 1; with labels: n_zones outside 1..32; a batch of more than 65535 studies.
+ * vh_batch_download_zones waits; every pointer is nullable; VH_ERR_ARG when vh_batch_zones has not been
+ * enqueued since the last run or the last call that forgets the run.  The kernel-timing class is
+ * "zones_b" (vh_batch_kernel_time reads it; vh_batch_kernel_names does not list it).
+ *
+ * The kernels take every shape a batch accepts in one form: the profile, map and count sweeps give a
+ * workgroup 256 consecutive (column, slice) pairs and a slab of rows; what does not fit a workgroup's
+ * LDS (the slice profile of Z >= 256, the part tables' profiles of R + C + Z > 12288) goes through
+ * global integer atomics or global reads.
+ *
+ * vh_zone_parts / vh_zone_split are the rule on the host, no device needed: the parts of one axis from
+ * its profile (n entries, each >= 0) with bounds = {lo, hi}, and the split column of a column profile.
+ * VH_ERR_ARG for a null pointer, n < 1, p outside 1..32, by not VH_ZONE_*, a negative entry or a total
+ * above 2^57.
+ *
+ * vh_zones is the host-buffer form on the context's scratch batch: the post-N4 chain of vh_vdp on n4
+ * and mask with thresh, then defect (nullable: the chain's map stays) as the resident defect map, then
+ * the analysis.  VH_ERR_EMPTY for an empty-mask study, after the outputs are written. */
+#define VH_ZONE_EXTENT 0
+#define VH_ZONE_COUNT 1
+#define VH_ZONE_COLS 8     /* mask, defect (on the mask), LB class 1..6 */
+int vh_zone_parts(const int64_t *profile, int64_t n, int32_t p, int by, uint8_t *part /* [n] */, int32_t bounds[2]);
+int vh_zone_split(const int64_t *profile, int64_t n, int32_t *s);
+int vh_batch_zones(vh_batch *b, const uint8_t *labels /* [nb][V], nullable */, int32_t n_zones,
+                   const int32_t parts[3], int lateral, int by, int norm, int32_t n_bins, float hi);   /* enqueue only */
+int vh_batch_download_zones(vh_batch *b, uint8_t *map /* [nb][V] */, int64_t *counts /* [nb][K+1][8] */,
+                            uint32_t *hist /* [nb][K+1][n_bins] */, int64_t *stats /* [nb][K+1][4] */,
+                            int32_t *geom /* [nb][8] */);   /* waits; all nullable */
+int vh_zones(vh_ctx *ctx, const float *n4, const uint8_t *mask, const uint8_t *defect /* nullable */, int64_t R,
+             int64_t C, int64_t Z, int64_t batch, float thresh, const uint8_t *labels /* nullable */, int32_t n_zones,
+             const int32_t parts[3], int lateral, int by, int norm, int32_t n_bins, float hi, uint8_t *map,
+             int64_t *counts, uint32_t *hist, int64_t *stats, int32_t *geom);
 
 /* ---- the denoise option of a device-resident batch ("Denoise Option", Vent_Analysis.py:1025) -------
  * An in-plane non-local-means filter of the resident HPvent with a Tukey bisquare weight.  Every

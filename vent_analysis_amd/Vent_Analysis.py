@@ -283,6 +283,36 @@ class Vent_Analysis:
             out['vdp_from_slices'] = 100 * np.float64(sl[:, 1].sum()) / n_mask
         return out
 
+    def regional_vdp(self, parts=(3, 1, 1), lateral=True, by='extent', labels=None, n_zones=None, norm='mean',
+                     bins=100, hi=1.5):
+        """The regional analysis (build-defined): the VDP, the linear-binning class counts and the
+        histogram of N4HPvent / d of every lung zone, counted on the GPU from N4HPvent, the mask and
+        ``defectArray`` as it stands (select_defect's map included).  Geometric zones: ``parts`` (rows,
+        columns, slices) cut the mask's bounding box ``by`` 'extent' or by voxel 'count', and
+        ``lateral`` splits the columns into the two lungs at the emptiest column of the middle half
+        (``parts[1]`` must then be 1); zone = 1 + (row part * columns + column part or side) * slice
+        parts + slice part.  ``labels`` [R][C][Z] gives the caller's zones 1..``n_zones`` instead (lobes
+        from a registered CT); a mask voxel no label claims is zone 0.  Needs calculate_VDP first.
+        Returns a dict and sets nothing on the object: ``map`` uint8 [R][C][Z]; ``counts`` int64
+        [K + 1][8] (mask, defect, LB class 1..6 per zone); ``hist`` uint32 [K + 1][bins] over [0, ``hi``);
+        ``edges`` float64 [bins + 1]; ``stats`` int64 [K + 1][4] (n_in, n_below, n_over, sum_fx);
+        ``geom`` int32 [8] (the mask's bounds on the three axes, the split column or -1, 0);
+        ``zone_vdp`` float64 [K + 1], 100 * defect / mask, NaN for an empty zone; ``zone_mean`` float64
+        [K + 1], the mean normalised signal; ``n_zones`` K."""
+        if isinstance(self.N4HPvent, str) or isinstance(self.defectArray, str):
+            raise ValueError("regional_vdp: N4HPvent / defectArray are not set (run calculate_VDP first)")
+        mask_u8, _ = _mask_value(self.mask)
+        n4 = np.asarray(self.N4HPvent, dtype=np.float32)
+        a = _lib._zones_args(parts, lateral, by, None if labels is None else np.asarray(labels)[None], n_zones,
+                             norm, bins, hi, (1,) + n4.shape)
+        with _lib.pooled_batch(*n4.shape, 1, device=self.device) as B:
+            B.upload(n4[None], mask_u8[None])
+            B.run(B.options(do_n4=False, do_snr=False, do_kmeans=False, vox=self.vox))
+            B.upload_defect((np.asarray(self.defectArray) != 0)[None])
+            B.zones(parts, lateral, by, a["labels"], a["n_zones"] or None, norm, bins, hi)
+            out = B.download_zones()
+        return {k: (v if k in ('edges', 'n_zones') else np.array(v[0])) for k, v in out.items()}
+
     def ventilation_heterogeneity(self, radius=1, min_count=None, bins=100, hi=1.0, exclude_defect=False):
         """The local ventilation heterogeneity (build-defined): the coefficient of variation of
         N4HPvent over the masked pixels of the (2 ``radius`` + 1)^2 in-plane window of every masked

@@ -394,6 +394,12 @@ _SIGS = {
     "vh_batch_filter_components": ([_P, ct.c_int, ct.c_int, _P, _P, _P], ct.c_int),
     "vh_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, ct.c_int32, _P, _P, _P, _P], ct.c_int),
     "vh_filter_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, _P, _P, _P], ct.c_int),
+    "vh_zone_parts": ([_P, _I64, ct.c_int32, ct.c_int, _P, _P], ct.c_int),
+    "vh_zone_split": ([_P, _I64, _P], ct.c_int),
+    "vh_batch_zones": ([_P, _P, ct.c_int32, _P, ct.c_int, ct.c_int, ct.c_int, ct.c_int32, ct.c_float], ct.c_int),
+    "vh_batch_download_zones": ([_P, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_zones": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, ct.c_float, _P, ct.c_int32, _P, ct.c_int, ct.c_int,
+                  ct.c_int, ct.c_int32, ct.c_float, _P, _P, _P, _P, _P], ct.c_int),
     "vh_batch_noise_sigma": ([_P, _P], ct.c_int),
     "vh_batch_denoise": ([_P, _P, ct.c_float, ct.c_int, ct.c_int, ct.c_int], ct.c_int),
     "vh_batch_download_hp": ([_P, _P], ct.c_int),
@@ -898,6 +904,143 @@ def core_rind(mask, defect=None, edges=(1.5, 3.5), device=0, thresholds=None):
     c.check(c.L.vh_core_rind(c.h, _ptr(m), _ptr(d), *m.shape[1:], B, _ptr(thr), thr.size,
                              _ptr(out), _ptr(counts), _ptr(stats)), "vh_core_rind")
     return dict(d2=out, counts=counts, stats=stats, thresholds=thr, band_vdp=band_vdp(counts))
+
+
+VH_ZONE_EXTENT, VH_ZONE_COUNT = range(2)   # vh_batch_zones: how an axis is cut into parts
+VH_ZONE_COLS = 8                           # counts columns: mask, defect (on the mask), LB class 1..6
+_ZONE_BYS = {"extent": VH_ZONE_EXTENT, "count": VH_ZONE_COUNT}
+ZONE_MAX = 32                              # the most zones, and the most parts of an axis
+
+
+def zone_by(by) -> int:
+    """'extent' | 'count' or the VH_ZONE_* ints -> the int; anything else raises ValueError."""
+    return _named_int(by, _ZONE_BYS, "zones: by")
+
+
+def _zones_args(parts=(3, 1, 1), lateral=True, by="extent", labels=None, n_zones=None, norm="mean", bins=100,
+                hi=1.5, shape=None):
+    """The checked arguments of vh_batch_zones as a dict: ``labels`` (uint8, contiguous, of ``shape``
+    when given, or None), ``n_zones``, ``parts`` int32 [3], ``lateral``, ``by``, ``norm``, ``bins``,
+    ``hi`` and ``K``, the zones without zone 0.  With ``labels`` the geometric arguments are not looked
+    at and ``n_zones`` None is the largest label.  ValueError for what the library would refuse, so the
+    message names the argument."""
+    def whole(v, what):
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"zones: {what} is an int, got {v!r}")
+        return int(v)
+    norm = norm_source(norm)
+    if norm not in (VH_NORM_MEAN, VH_NORM_P99):
+        raise ValueError(f"zones: norm is 'mean' or 'p99' or 0..1, got {norm!r}")
+    bins = whole(bins, "bins")
+    if not 1 <= bins <= 256:
+        raise ValueError(f"zones: bins must be 1..256, got {bins!r}")
+    h = np.float32(hi)
+    if not (np.isfinite(h) and 0 < h <= 64):
+        raise ValueError(f"zones: hi must be finite, > 0 and <= 64, got {hi!r}")
+    out = dict(labels=None, n_zones=0, parts=np.ones(3, np.int32), lateral=0, by=VH_ZONE_EXTENT, norm=norm,
+               bins=bins, hi=float(h))
+    if labels is not None:
+        lab = np.asarray(labels)
+        if lab.dtype == np.bool_ or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"zones: labels is an integer volume, got dtype {lab.dtype}")
+        if shape is not None and lab.shape != tuple(shape):
+            raise ValueError(f"zones: labels must have shape {tuple(shape)}, got {lab.shape}")
+        if lab.dtype != np.uint8:   # (a label outside a byte is no zone: 0, like every byte above K)
+            lab = np.where((lab >= 0) & (lab <= 255), lab, 0)
+        n_zones = int(lab.max()) if n_zones is None and lab.size else whole(0 if n_zones is None else n_zones, "n_zones")
+        if not 1 <= n_zones <= ZONE_MAX:
+            raise ValueError(f"zones: n_zones must be 1..{ZONE_MAX}, got {n_zones!r}")
+        out.update(labels=np.ascontiguousarray(lab, dtype=np.uint8), n_zones=n_zones, K=n_zones)
+        return out
+    by = zone_by(by)
+    if isinstance(lateral, (float, str)) or lateral not in (0, 1, False, True):
+        raise ValueError(f"zones: lateral is a bool, got {lateral!r}")
+    lateral = int(lateral)
+    p = np.asarray(parts)
+    if p.shape != (3,) or p.dtype == np.bool_ or not np.issubdtype(p.dtype, np.integer):
+        raise ValueError(f"zones: parts is three ints (rows, columns, slices), got {parts!r}")
+    p = p.astype(np.int64)
+    if (p < 1).any():
+        raise ValueError(f"zones: every part count must be >= 1, got {parts!r}")
+    if lateral and p[1] != 1:
+        raise ValueError(f"zones: lateral takes the column axis, parts[1] must be 1, got {parts!r}")
+    K = int(p[0] * (2 if lateral else p[1]) * p[2])
+    if K > ZONE_MAX:
+        raise ValueError(f"zones: at most {ZONE_MAX} zones, got {K} from parts {parts!r}"
+                         + (" with lateral" if lateral else ""))
+    out.update(parts=np.ascontiguousarray(p, dtype=np.int32), lateral=lateral, by=by, K=K)
+    return out
+
+
+def zone_vdp(counts):
+    """float64 100 * defect / mask of each zone from ``counts`` [...][8]; NaN for an empty zone."""
+    return band_vdp(np.asarray(counts, dtype=np.int64)[..., :2])
+
+
+def zone_mean(stats):
+    """The mean normalised signal of each zone from its ``stats`` row(s) (n_in, n_below, n_over,
+    sum_fx): float64 sum_fx / 2^24 / n_in over the in-range voxels; NaN where n_in == 0."""
+    return het_index(stats)
+
+
+def _zones_dict(a, m, c, h, s, g):
+    return dict(map=m, counts=c, hist=h, edges=dist_edges(a["bins"], a["hi"]), stats=s, geom=g,
+                zone_vdp=zone_vdp(c), zone_mean=zone_mean(s), n_zones=a["K"])
+
+
+def zone_parts(profile, p, by="extent"):
+    """The parts of one axis from its mask profile (vh_zone_parts; no device): (part uint8 [n],
+    (lo, hi)).  ``profile`` holds the on voxels of every plane of the axis, ints >= 0."""
+    prof = np.ascontiguousarray(profile, dtype=np.int64)
+    if prof.ndim != 1 or prof.size < 1:
+        raise ValueError(f"zone_parts: profile is a non-empty sequence of ints, got shape {prof.shape}")
+    if isinstance(p, (bool, float)) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= ZONE_MAX:
+        raise ValueError(f"zone_parts: p must be 1..{ZONE_MAX}, got {p!r}")
+    part = np.zeros(prof.size, np.uint8)
+    bounds = np.zeros(2, np.int32)
+    if lib().vh_zone_parts(_ptr(prof), prof.size, int(p), zone_by(by), _ptr(part), _ptr(bounds)) != VH_OK:
+        raise ValueError("zone_parts: the profile holds a negative entry or its total exceeds 2^57")
+    return part, (int(bounds[0]), int(bounds[1]))
+
+
+def zone_split(profile):
+    """The lateral split column of a column profile (vh_zone_split; no device)."""
+    prof = np.ascontiguousarray(profile, dtype=np.int64)
+    if prof.ndim != 1 or prof.size < 1:
+        raise ValueError(f"zone_split: profile is a non-empty sequence of ints, got shape {prof.shape}")
+    s = ct.c_int32(0)
+    if lib().vh_zone_split(_ptr(prof), prof.size, ct.byref(s)) != VH_OK:
+        raise ValueError("zone_split: the profile holds a negative entry or its total exceeds 2^57")
+    return int(s.value)
+
+
+def zones(n4, mask, defect=None, parts=(3, 1, 1), lateral=True, by="extent", labels=None, n_zones=None,
+          norm="mean", bins=100, hi=1.5, thresh=0.6, device=0, map=True):
+    """The regional analysis from host arrays (vh_zones; the spec is in include/vent_hip.h): the
+    post-N4 chain on ``n4`` and ``mask`` (3-D volumes or 4-D batches), ``defect`` (None: the chain's
+    mean-anchored map at ``thresh``) as the defect map, then the zones.  Returns the dict of
+    Batch.download_zones.  IndexError for an empty-mask study, like vdp()."""
+    c = context(device)
+    n = as_batch(n4, np.float32)
+    m = as_batch(_mask_u8(mask), np.uint8)
+    d = None if defect is None else as_batch(_mask_u8(defect), np.uint8)
+    if n.shape != m.shape or (d is not None and d.shape != m.shape):
+        raise ValueError("N4, mask and defect shapes differ")
+    if labels is not None and np.ndim(labels) == 3:
+        labels = np.asarray(labels)[None]
+    a = _zones_args(parts, lateral, by, labels, n_zones, norm, bins, hi, n.shape)
+    B, R, C, Z = n.shape
+    K1 = a["K"] + 1
+    out = np.empty(n.shape, np.uint8) if map else None
+    counts = np.zeros((B, K1, VH_ZONE_COLS), np.int64)
+    hist = np.zeros((B, K1, a["bins"]), np.uint32)
+    stats = np.zeros((B, K1, 4), np.int64)
+    geom = np.zeros((B, 8), np.int32)
+    c.check(c.L.vh_zones(c.h, _ptr(n), _ptr(m), _ptr(d), R, C, Z, B, ct.c_float(thresh), _ptr(a["labels"]),
+                         a["n_zones"], _ptr(a["parts"]), a["lateral"], a["by"], a["norm"], a["bins"],
+                         ct.c_float(a["hi"]), _ptr(out), _ptr(counts), _ptr(hist), _ptr(stats), _ptr(geom)),
+            "vh_zones")
+    return _zones_dict(a, out, counts, hist, stats, geom)
 
 
 VH_CC_DEFECT, VH_CC_MASK = range(2)     # vh_batch_components sources
@@ -1528,6 +1671,43 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_components(self.h, _ptr(r), _ptr(sz), _ptr(counts), _ptr(stats)),
                        "vh_batch_download_components")
         return dict(root=r, size=sz, counts=counts, stats=stats, edges=e.copy())
+
+    def zones(self, parts=(3, 1, 1), lateral=True, by="extent", labels=None, n_zones=None, norm="mean", bins=100,
+              hi=1.5):
+        """Enqueue the regional analysis of every study (vh_batch_zones; the spec is in
+        include/vent_hip.h): a zone map and per zone the mask, defect and LB class counts and the
+        histogram of float32(N4 / d) in ``bins`` bins of [0, hi).  Geometric zones: ``parts`` (rows,
+        columns, slices) cut the mask's bounding box ``by`` 'extent' or by voxel 'count', and
+        ``lateral`` splits the columns into the left and the right lung at the emptiest column of the
+        middle half (``parts[1]`` must then be 1).  ``labels``, uint8 [B][R][C][Z], gives the caller's
+        zones 1..``n_zones`` instead (None: the largest label); any other byte on the mask is zone 0.
+        Read-only; download_zones fetches the last call's result.  Needs a run."""
+        a = _zones_args(parts, lateral, by, labels, n_zones, norm, bins, hi, self.shape)
+        self.ctx.check(self.L.vh_batch_zones(self.h, _ptr(a["labels"]), a["n_zones"], _ptr(a["parts"]), a["lateral"],
+                                             a["by"], a["norm"], a["bins"], ct.c_float(a["hi"])), "vh_batch_zones")
+        a["labels"] = None
+        self._zn = a
+
+    def download_zones(self, map=True):
+        """The last zones() as a dict: ``map`` uint8 [B][R][C][Z], the zone 1..K of every mask voxel (0
+        off the mask, and for a mask voxel no label claims; None with ``map=False``: only counts come
+        back); ``counts`` int64 [B][K + 1][8] with columns mask, defect, LB class 1..6; ``hist`` uint32
+        [B][K + 1][bins]; ``edges`` float64 [bins + 1], for display; ``stats`` int64 [B][K + 1][4]: n_in,
+        n_below, n_over, sum_fx; ``geom`` int32 [B][8]: lo_r, hi_r, lo_c, hi_c, lo_z, hi_z, the split
+        column (-1: none), 0; ``zone_vdp`` float64 [B][K + 1], 100 * defect / mask, NaN for an empty
+        zone; ``zone_mean`` float64 [B][K + 1], the mean normalised signal; ``n_zones`` K."""
+        a = getattr(self, "_zn", dict(K=0, bins=0, hi=1.0))
+        B, K1 = self.shape[0], a["K"] + 1
+        out = self.ctx.pinned.array(self.shape, np.uint8) if map else None   # page-locked: the link rate
+        counts = np.zeros((B, K1, VH_ZONE_COLS), np.int64)
+        hist = np.zeros((B, K1, a["bins"]), np.uint32)
+        stats = np.zeros((B, K1, 4), np.int64)
+        geom = np.zeros((B, 8), np.int32)
+        self.ctx.check(self.L.vh_batch_download_zones(self.h, _ptr(out), _ptr(counts), _ptr(hist), _ptr(stats),
+                                                      _ptr(geom)), "vh_batch_download_zones")
+        if not a["bins"]:   # (unreachable: the library refuses a download before any zones())
+            raise ValueError("download_zones: zones() has not been called")
+        return _zones_dict(a, out, counts, hist, stats, geom)
 
     def filter_components(self, source="defect", conn=6, min_size=1, keep_largest=0):
         """Clear the small components of the resident defect map or mask (vh_batch_filter_components):

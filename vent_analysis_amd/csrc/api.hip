@@ -16,6 +16,7 @@
 
 #include "vh_internal.h"
 #include "resample_host.h"
+#include "zones_host.h"
 
 // ---------------------------------------------------------------------------------------------
 // timing
@@ -1439,6 +1440,148 @@ int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, in
         if (out) HIP_TRY(hipMemcpyAsync(out, b->d_mask, (size_t)batch * b->V, hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
     })
+}
+
+// ---- the regional analysis of a device-resident batch (zones.hip) ------------------------------------
+// the argument checks (host only: nothing is enqueued before they pass); returns K
+static int32_t check_zones(const uint8_t *labels, int32_t n_zones, const int32_t *parts, int lateral, int by, int norm,
+                           int32_t n_bins, float hi) {
+    if (norm != VH_NORM_MEAN && norm != VH_NORM_P99)
+        throw VhError{VH_ERR_ARG, "norm must be VH_NORM_MEAN or VH_NORM_P99"};
+    if (n_bins < 1 || n_bins > 256) throw VhError{VH_ERR_ARG, "n_bins must be 1..256"};
+    if (!std::isfinite(hi) || !(hi > 0.0f) || !(hi <= 64.0f))
+        throw VhError{VH_ERR_ARG, "hi must be finite, > 0 and <= 64"};
+    if (labels) {
+        if (n_zones < 1 || n_zones > ZN_MAX_PARTS) throw VhError{VH_ERR_ARG, "n_zones must be 1..32"};
+        return n_zones;
+    }
+    if (by != VH_ZONE_EXTENT && by != VH_ZONE_COUNT) throw VhError{VH_ERR_ARG, "by must be VH_ZONE_EXTENT or VH_ZONE_COUNT"};
+    if (!parts) throw VhError{VH_ERR_ARG, "null parts"};
+    if (lateral != 0 && lateral != 1) throw VhError{VH_ERR_ARG, "lateral must be 0 or 1"};
+    int64_t K = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (parts[a] < 1) throw VhError{VH_ERR_ARG, "every part count must be >= 1"};
+        if (parts[a] > ZN_MAX_PARTS) throw VhError{VH_ERR_ARG, "more than 32 zones"};
+        K *= parts[a];
+    }
+    if (lateral && parts[1] != 1) throw VhError{VH_ERR_ARG, "lateral needs parts[1] = 1"};
+    if (lateral) K *= 2;
+    if (K > ZN_MAX_PARTS) throw VhError{VH_ERR_ARG, "more than 32 zones"};
+    return (int32_t)K;
+}
+
+// Enqueue the four kernels over what the last run left resident.  They write the zone buffers only, so
+// nothing another call on the batch reads changes (the CI stays fresh).
+static void batch_zones(vh_batch *b, const uint8_t *labels, int32_t K, const int32_t *parts, int lateral, int by,
+                        int norm, int32_t n_bins, float hi) {
+    b->state.need_run();
+    if (!vh_zones_takes(b)) throw VhError{VH_ERR_ARG, "zones: more than 65535 studies"};
+    const size_t nb = (size_t)b->nb, L = (size_t)(b->R + b->C + b->Z), K1 = ZN_MAX_PARTS + 1;   // the largest K: no regrowth
+    b->d_zn_prof.reserve(nb * L);
+    b->d_zn_tab.reserve(nb * L);
+    b->d_zn_geom.reserve(nb * 8);
+    b->d_zn_map.reserve(nb * b->V);
+    b->d_zn_counts.reserve(nb * K1 * VH_ZONE_COLS);
+    b->d_zn_hist.reserve(nb * K1 * 256);
+    b->d_zn_stats.reserve(nb * K1 * 4);
+    static const int32_t one[3] = {1, 1, 1};
+    if (labels) {   // the caller's buffer is free once the call returns: wait for the copy, and for it alone
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipMemcpyAsync(b->d_zn_map, labels, nb * b->V, hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipEventRecord(ev, b->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ev);
+        (void)hipEventDestroy(ev);
+        HIP_TRY(e);
+    }
+    const float scale = (float)n_bins / hi;   // once, in float32: the kernel multiplies by it
+    vh_zones_launch(b, labels != nullptr, K, labels ? one : parts, labels ? 0 : lateral, labels ? VH_ZONE_EXTENT : by,
+                    norm, n_bins, hi, scale);
+    b->state.zones_enqueued(K, n_bins);
+}
+
+static void batch_download_zones(vh_batch *b, uint8_t *map, int64_t *counts, uint32_t *hist, int64_t *stats,
+                                 int32_t *geom) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb, K1 = (size_t)b->state.zone_k() + 1;
+    if (map) HIP_TRY(hipMemcpyAsync(map, b->d_zn_map, nb * b->V, hipMemcpyDeviceToHost, st));
+    if (counts)
+        HIP_TRY(hipMemcpyAsync(counts, b->d_zn_counts, sizeof(int64_t) * nb * K1 * VH_ZONE_COLS, hipMemcpyDeviceToHost, st));
+    if (hist)
+        HIP_TRY(hipMemcpyAsync(hist, b->d_zn_hist, sizeof(uint32_t) * nb * K1 * b->state.zone_bins(), hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, b->d_zn_stats, sizeof(int64_t) * nb * K1 * 4, hipMemcpyDeviceToHost, st));
+    if (geom) HIP_TRY(hipMemcpyAsync(geom, b->d_zn_geom, sizeof(int32_t) * nb * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_zones(vh_batch *b, const uint8_t *labels, int32_t n_zones, const int32_t parts[3], int lateral, int by,
+                   int norm, int32_t n_bins, float hi) {
+    BATCH_TRY(b, {
+        const int32_t K = check_zones(labels, n_zones, parts, lateral, by, norm, n_bins, hi);
+        batch_zones(b, labels, K, parts, lateral, by, norm, n_bins, hi);
+    })
+}
+
+int vh_batch_download_zones(vh_batch *b, uint8_t *map, int64_t *counts, uint32_t *hist, int64_t *stats, int32_t *geom) {
+    BATCH_TRY(b, {
+        b->state.need_zones();
+        batch_download_zones(b, map, counts, hist, stats, geom);
+    })
+}
+
+int vh_zones(vh_ctx *ctx, const float *n4, const uint8_t *mask, const uint8_t *defect, int64_t R, int64_t C, int64_t Z,
+             int64_t batch, float thresh, const uint8_t *labels, int32_t n_zones, const int32_t parts[3], int lateral,
+             int by, int norm, int32_t n_bins, float hi, uint8_t *map, int64_t *counts, uint32_t *hist, int64_t *stats,
+             int32_t *geom) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!n4 || !mask) throw VhError{VH_ERR_ARG, "null buffer"};
+        const int32_t K = check_zones(labels, n_zones, parts, lateral, by, norm, n_bins, hi);
+        check_dims(R, C, Z, batch);
+        const vh_run_opts o = chain_only_opts(thresh, false, false, ctx->profile);
+        vh_batch *b = run_host_arrays(ctx, nullptr, n4, mask, R, C, Z, batch, o);
+        if (defect) {   // (pageable source, and batch_download_zones waits before the call returns)
+            HIP_TRY(hipMemcpyAsync(b->d_defect, defect, (size_t)batch * b->V, hipMemcpyHostToDevice, b->stream));
+            b->state.defect_replaced();
+        }
+        batch_zones(b, labels, K, parts, lateral, by, norm, n_bins, hi);
+        batch_download_zones(b, map, counts, hist, stats, geom);
+        throw_if_empty_mask(read_scalars(b));
+    })
+}
+
+// the rule on the host (zones_host.h): no device, no context
+static bool zone_profile_ok(const int64_t *profile, int64_t n) {
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (profile[i] < 0 || profile[i] > ((int64_t)1 << 57) - total) return false;
+        total += profile[i];
+    }
+    return true;
+}
+
+int vh_zone_parts(const int64_t *profile, int64_t n, int32_t p, int by, uint8_t *part, int32_t bounds[2]) {
+    if (!profile || !part || !bounds || n < 1 || n > INT32_MAX || p < 1 || p > ZN_MAX_PARTS ||
+        (by != VH_ZONE_EXTENT && by != VH_ZONE_COUNT) || !zone_profile_ok(profile, n))
+        return VH_ERR_ARG;
+    int32_t lo, hi;
+    int64_t total;
+    zn_bounds(profile, n, lo, hi, total);
+    zn_axis_parts(profile, n, p, by, lo, hi, total, part);
+    bounds[0] = lo;
+    bounds[1] = hi;
+    return VH_OK;
+}
+
+int vh_zone_split(const int64_t *profile, int64_t n, int32_t *s) {
+    if (!profile || !s || n < 1 || n > INT32_MAX || !zone_profile_ok(profile, n)) return VH_ERR_ARG;
+    int32_t lo, hi;
+    int64_t total;
+    zn_bounds(profile, n, lo, hi, total);
+    *s = zn_split(profile, lo, hi);
+    return VH_OK;
 }
 
 // ---- the denoise option of a device-resident batch (denoise.hip) --------------------------------

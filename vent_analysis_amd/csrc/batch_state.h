@@ -36,6 +36,9 @@ public:
         int32_t cr_bands = 0;        // its n_thr + 1 (while core_rind)
         bool components = false;     // vh_batch_components has been enqueued, and no filter has reused its buffers
         int32_t cc_classes = 0;      // its n_edges + 1 (while components)
+        bool zones = false;          // vh_batch_zones has been enqueued
+        int32_t zone_k = 0;          // its K, the zones without zone 0 (while zones)
+        int32_t zone_bins = 0;       // its n_bins (while zones)
         // an input, like the resident HPvent and mask: no transition but its own changes it
         bool proton = false;         // d_proton holds the batch's proton volumes
         bool proton_src = false;     // d_proton_src holds the proton on its own grid (vh_batch_upload_proton_src)
@@ -56,6 +59,7 @@ public:
     void heterogeneity_enqueued(int32_t bins) { f_.heterogeneity = true; f_.het_bins = bins; }
     void core_rind_enqueued(int32_t bands) { f_.core_rind = true; f_.cr_bands = bands; }
     void components_enqueued(int32_t classes) { f_.components = true; f_.cc_classes = classes; }
+    void zones_enqueued(int32_t k, int32_t bins) { f_.zones = true; f_.zone_k = k; f_.zone_bins = bins; }
     void components_filtered() { f_.components = false; }   // vh_batch_filter_components relabelled into the same buffers
     void proton_uploaded() { f_.proton = true; }
     void proton_src_uploaded() { f_.proton_src = true; }
@@ -85,6 +89,9 @@ public:
         need(f_.components, "vh_batch_components has not been called since the last run, the last edit of the inputs "
                             "or the last vh_batch_filter_components");
     }
+    void need_zones() const {
+        need(f_.zones, "vh_batch_zones has not been called since the last run or the last edit of the inputs");
+    }
     void need_proton() const { need(f_.proton, "no proton resident: vh_batch_upload_proton first"); }
     void need_proton_src() const {
         need(f_.proton_src, "no proton source resident: vh_batch_upload_proton_src first");
@@ -106,6 +113,9 @@ public:
     int32_t cr_bands() const { return f_.cr_bands; }
     bool has_components() const { return f_.components; }
     int32_t cc_classes() const { return f_.cc_classes; }
+    bool has_zones() const { return f_.zones; }
+    int32_t zone_k() const { return f_.zone_k; }
+    int32_t zone_bins() const { return f_.zone_bins; }
     const Fields &fields() const { return f_; }   // everything, read-only (tests/batch_state_check.cpp)
 
 private:
@@ -115,7 +125,7 @@ private:
     void clear_derived() {
         f_.labels = f_.selection = f_.ci_fresh = false;
         f_.layout = f_.overlay = f_.montage = f_.distribution = f_.heterogeneity = f_.core_rind = false;
-        f_.components = false;
+        f_.components = f_.zones = false;
     }
     static void need(bool ok, const char *msg) { if (!ok) throw VhError{VH_ERR_ARG, msg}; }
 };

@@ -300,6 +300,14 @@ struct vh_batch {
     Buf<int32_t> d_cc_keep;          // [nb] its keep_largest
     Buf<unsigned long long> d_cc_picks;    // [nb][8] its picks: the k largest keys of each study, in order
     Buf<unsigned long long> d_cc_kept;     // [nb][2] the components and the voxels it kept
+    // vh_batch_zones (zones.hip): every buffer on first demand
+    Buf<uint32_t> d_zn_prof;         // [nb][R + C + Z] the mask's on voxels of every row, column and slice
+    Buf<uint8_t> d_zn_tab;           // [nb][R + C + Z] the part of every row, column (or its side) and slice
+    Buf<int32_t> d_zn_geom;          // [nb][8] lo_r, hi_r, lo_c, hi_c, lo_z, hi_z, s, 0
+    Buf<uint8_t> d_zn_map;           // [nb][V] the last call's zone maps
+    Buf<unsigned long long> d_zn_counts;   // [nb][state.zone_k() + 1][VH_ZONE_COLS]
+    Buf<uint32_t> d_zn_hist;         // [nb][state.zone_k() + 1][state.zone_bins()]
+    Buf<unsigned long long> d_zn_stats;    // [nb][state.zone_k() + 1][4] n_in, n_below, n_over, sum_fx
     // vh_batch_edit_mask / vh_batch_download_mask (mask_edit.hip): on first demand.  The edits' scratch
     // volumes are d_border (the morphology's other mask) and d_lb (the strokes): a run rewrites both
     Buf<int32_t> d_me_radius;        // [nb] the last edit's radii
@@ -562,6 +570,13 @@ void vh_cc_launch(vh_batch *b, const uint8_t *src, int conn, const uint32_t *edg
                   uint32_t *size, unsigned long long *d_counts, unsigned long long *d_stats);
 void vh_cc_filter_launch(vh_batch *b, uint8_t *src, const int *root, const uint32_t *size, const uint32_t *d_min,
                          const int32_t *d_keep, int kmax, unsigned long long *d_picks, unsigned long long *d_kept);
+// zones.hip: the zone maps (labels: d_zn_map holds the caller's bytes, else the rule of zones_host.h over
+// parts, lateral, by) into d_zn_map with the geometry in d_zn_geom, and the counts of the K + 1 zones over
+// the resident N4, mask, defect map, LB classes and zone map into d_zn_counts / d_zn_hist / d_zn_stats
+// (zeroed here); vh_zones_takes: the grid fits
+bool vh_zones_takes(const vh_batch *b);
+void vh_zones_launch(vh_batch *b, bool labels, int K, const int32_t parts[3], int lateral, int by, int norm,
+                     int n_bins, float hi, float scale);
 // mask_edit.hip: one disc dilation (erode 0) or erosion (erode 1) of every study, src -> dst (two
 // mask volumes of the batch), with d_radius [nb] in 0..5 (0: the study is copied);
 // vh_mask_edit_takes: the grid fits.  vh_mask_paint_launch: mask = paint(mask != 0, strokes != 0) in
