@@ -54,6 +54,10 @@
  *                defect map or mask: the canonical root and the size of every voxel's component, counts
  *                per size class, and a filter by size and by rank (build-defined); kernel-timing class
  *                "comp_b", not listed
+ *   vh_batch_defect_table / vh_batch_download_defect_table  the defect table: one row per component of
+ *                the last vh_batch_components, largest first, with exact integer moments, the bounding
+ *                box, the exposed-face counts and fixed-point signal sums (build-defined); kernel-timing
+ *                class "dtab_b", not listed
  *   vh_batch_zones / vh_batch_download_zones / vh_zones / vh_zone_parts / vh_zone_split  the regional
  *                analysis: a zone map (left / right lung, thirds, a grid of parts, or the caller's label
  *                volume) and per zone the mask, defect and linear-binning class counts and the histogram
@@ -575,6 +579,66 @@ int vh_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z
                   const uint32_t *edges, int32_t n_edges, int32_t *root, uint32_t *size, int64_t *counts, int64_t *stats);
 int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, int64_t Z, int64_t batch, int conn,
                          const uint32_t *min_size, const int32_t *keep_largest, uint8_t *out, int64_t *kept);
+
+/* ---- the defect table of a device-resident batch ----------------------------------------------------
+ * Where the big defects are, how large each is, how many slices it spans, how compact and how dark it
+ * is: one row per component, largest first, and only the table leaves the device (at most 147 KB per
+ * study).  Every entry is an integer combined by integer add / min / max, so nothing depends on the
+ * order in which threads add (tests/defect_table_ref.py is the same definition in numpy).
+ *
+ * The components are those of the last vh_batch_components: its source, its conn, and the resident
+ * root and size maps.  A component's key and rank are the filter's: key (size, -root) ordered
+ * lexicographically, rank = the number of components of the study with a greater key.
+ *
+ * A component qualifies when size >= min_size[q] (uint32 [nb], each >= 1).  Row j (0 <= j < max_rows,
+ * max_rows 1..VH_DT_MAX_ROWS) holds the component of rank j if it qualifies: the qualifying components
+ * are a prefix of the rank order, so n_rows = min(n_qualifying, max_rows).  A row without a component
+ * has column 0 = -1 and every other column 0.
+ *
+ * rows int64 [nb][max_rows][VH_DT_COLS]:
+ *    0  root      the component's root            1  size      its voxels
+ *    2  sum_r     3  sum_c     4  sum_z           the sums of the voxel indices on each axis
+ *    5  min_r     6  max_r     7  min_c     8  max_c     9  min_z    10  max_z    inclusive bounds
+ *   11  faces_r  12  faces_c  13  faces_z         the exposed faces normal to each axis
+ *   14  n_sig    15  sum_fx   16  min_fx   17  max_fx    the signal columns
+ * Faces: for a voxel and each of its two neighbours along an axis, the face is exposed when the
+ * neighbour position lies outside the volume or the neighbour's root differs from the voxel's (under
+ * conn 4 and 8 slices never join, so faces_z = 2 size: the definition, not a special case).
+ * The signal columns, with norm = VH_NORM_MEAN or VH_NORM_P99: x is the N4 volume the last run's chain
+ * read, d the run's mean_anchor or p99, nv = float32(x / d).  A voxel counts when 0 <= nv < 64, and then
+ * fx = (int64)float32(nv * 16777216.0f), the heterogeneity's fixed point (the bound keeps sum_fx inside
+ * int64 at V < 2^31); negative, >= 64, NaN, infinite, or a zero divisor: not counted.  With n_sig = 0,
+ * or with norm = VH_DT_NO_SIGNAL, columns 14..17 are 0.
+ *
+ * stats int64 [nb][4] = n_rows, n_qualifying, the voxels in the rows, the voxels in the qualifying
+ * components; the table is truncated where n_rows < n_qualifying.
+ *
+ * vh_batch_defect_table enqueues only (min_size is read before it returns).  It reads the root and size
+ * maps (and x) and writes buffers of its own: nothing another call reads changes, so the CI stays fresh
+ * and vh_batch_download_components returns the same bytes before and after.  It may be called again;
+ * the download returns the last call's result.  A new vh_batch_components, vh_batch_filter_components,
+ * a new run and whatever forgets the run discard it: the events that replace or discard the labelling
+ * the rows refer to.  vh_batch_download_defect_table waits; both pointers are nullable.
+ *
+ * VH_ERR_ARG, with nothing enqueued: a null batch; a null min_size or a min_size of 0; max_rows outside
+ * 1..1024; norm not one of the three values; a norm that needs a run when there is none; no
+ * vh_batch_components result resident; a download without a vh_batch_defect_table since the last of
+ * the discarding events.  The kernel-timing class is "dtab_b" (vh_batch_kernel_time reads it;
+ * vh_batch_kernel_names does not list it).
+ *
+ * The kernels take every shape a batch accepts in one form.  Where a study has more qualifying
+ * components than rows, the max_rows-th greatest key is found by a radix select, 11 bits a pass over
+ * the 2 ceil(log2(V + 1)) bits of (size, -root); the at most 1024 keys at or above it are sorted in LDS
+ * (8 KB); a voxel finds its row by a binary search of its key in that list, and a workgroup combines
+ * the voxels of a row in LDS before one global 64-bit atomic per row and column.  Device memory, on
+ * first demand, per study: 147 456 B of rows (room for 1024), 8 KB of keys, 8 KB of digit histogram,
+ * 64 B of counters and selection state. */
+#define VH_DT_COLS 18
+#define VH_DT_MAX_ROWS 1024
+#define VH_DT_NO_SIGNAL (-1)
+int vh_batch_defect_table(vh_batch *b, const uint32_t *min_size /* [nb] */, int32_t max_rows, int norm);  /* enqueue only */
+int vh_batch_download_defect_table(vh_batch *b, int64_t *rows /* [nb][max_rows][VH_DT_COLS] */,
+                                   int64_t *stats /* [nb][4] */);  /* waits; both nullable */
 
 /* ---- the regional analysis of a device-resident batch ----------------------------------------------
  * Where in the lung the defects lie: the VDP, the class counts and the signal histogram of the left and

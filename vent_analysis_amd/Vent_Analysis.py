@@ -379,6 +379,38 @@ class Vent_Analysis:
                     voxel_mL=ml, size_mL=out['size'][0] * ml, largest_mL=int(st[2]) * ml,
                     class_mL=out['counts'][0][:, 1] * ml)
 
+    def defect_table(self, conn=6, min_size=1, max_rows=64, norm='mean'):
+        """The defect table (build-defined): one row per connected defect of ``defectArray`` as it
+        stands, largest first -- where it is, how large, how many slices it spans, how compact and how
+        dark -- built on the GPU from the component maps and N4HPvent; the spec is in
+        include/vent_hip.h.  Components under ``conn`` 4 | 8 (every slice on its own) | 6 | 26
+        neighbours; a defect needs ``min_size`` voxels; at most ``max_rows`` (1..1024) rows; ``norm``
+        'mean' | 'p99' divides N4HPvent for the signal columns, None leaves them out.  Needs
+        calculate_VDP first.  Returns a dict and sets nothing on the object: ``rows`` int64
+        [n_rows][18] (the columns of ``_lib.DT_COLUMNS``); ``columns``; ``n_rows``, ``n_qualifying``,
+        ``voxels_in_rows``, ``voxels_qualifying``; ``truncated``; and per row, from ``self.vox``, the
+        float64 arrays of ``_lib.table_metrics``: ``volume_mL``, ``centroid``, ``centroid_mm``,
+        ``extent``, ``surface_mm2``, ``sphericity``, ``mean``, ``min``, ``max``."""
+        if isinstance(self.N4HPvent, str) or isinstance(self.defectArray, str):
+            raise ValueError("defect_table: N4HPvent / defectArray are not set (run calculate_VDP first)")
+        _lib._components_args("defect", conn, ())
+        _lib._defect_table_args(min_size, max_rows, norm, 1)
+        mask_u8, _ = _mask_value(self.mask)
+        n4 = np.asarray(self.N4HPvent, dtype=np.float32)
+        with _lib.pooled_batch(*n4.shape, 1, device=self.device) as B:
+            B.upload(n4[None], mask_u8[None])
+            B.run(B.options(do_n4=False, do_snr=False, do_kmeans=False, vox=self.vox))
+            B.upload_defect((np.asarray(self.defectArray) != 0)[None])
+            B.components("defect", conn)
+            B.defect_table(min_size, max_rows, norm)
+            got = B.download_defect_table()
+        st = got['stats'][0]
+        rows = np.array(got['rows'][0][:int(st[0])])
+        out = dict(rows=rows, columns=_lib.DT_COLUMNS, n_rows=int(st[0]), n_qualifying=int(st[1]),
+                   voxels_in_rows=int(st[2]), voxels_qualifying=int(st[3]), truncated=bool(got['truncated'][0]))
+        out.update(_lib.table_metrics(rows, self.vox))
+        return out
+
     def filter_defects(self, min_size, conn=6):
         """Drop the defects of fewer than ``min_size`` voxels from ``defectArray`` (build-defined), on
         the GPU: the specks the linear-binning and k-means maps carry.  Components under ``conn`` 4 | 8

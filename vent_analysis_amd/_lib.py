@@ -392,6 +392,8 @@ _SIGS = {
     "vh_batch_components": ([_P, ct.c_int, ct.c_int, _P, ct.c_int32], ct.c_int),
     "vh_batch_download_components": ([_P, _P, _P, _P, _P], ct.c_int),
     "vh_batch_filter_components": ([_P, ct.c_int, ct.c_int, _P, _P, _P], ct.c_int),
+    "vh_batch_defect_table": ([_P, _P, ct.c_int32, ct.c_int], ct.c_int),
+    "vh_batch_download_defect_table": ([_P, _P, _P], ct.c_int),
     "vh_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, ct.c_int32, _P, _P, _P, _P], ct.c_int),
     "vh_filter_components": ([_P, _P, _I64, _I64, _I64, _I64, ct.c_int, _P, _P, _P, _P], ct.c_int),
     "vh_zone_parts": ([_P, _I64, ct.c_int32, ct.c_int, _P, _P], ct.c_int),
@@ -1130,6 +1132,55 @@ def filter_components(a, conn=6, min_size=1, keep_largest=0, device=0):
     return out, kept
 
 
+VH_DT_COLS, VH_DT_MAX_ROWS, VH_DT_NO_SIGNAL = 18, 1024, -1   # vh_batch_defect_table
+DT_COLUMNS = ("root", "size", "sum_r", "sum_c", "sum_z", "min_r", "max_r", "min_c", "max_c", "min_z", "max_z",
+              "faces_r", "faces_c", "faces_z", "n_sig", "sum_fx", "min_fx", "max_fx")
+
+
+def _defect_table_args(min_size, max_rows, norm, n):
+    """(min_size uint32 [n], max_rows int, norm int) for vh_batch_defect_table: ``min_size`` >= 1, a
+    scalar or one int per study; ``max_rows`` 1..1024; ``norm`` None (no signal columns) | 'mean' |
+    'p99'.  ValueError for what the library would refuse, so the message names the argument."""
+    ms = _per_study_ints(min_size, n, 1, 2 ** 32 - 1, np.uint32, "min_size")
+    if (isinstance(max_rows, (bool, float)) or not isinstance(max_rows, (int, np.integer))
+            or not 1 <= int(max_rows) <= VH_DT_MAX_ROWS):
+        raise ValueError(f"defect_table: max_rows must be an int in 1..{VH_DT_MAX_ROWS}, got {max_rows!r}")
+    if norm is not None and not (isinstance(norm, str) and norm in _NORM_SOURCES):
+        raise ValueError(f"defect_table: norm is None, 'mean' or 'p99', got {norm!r}")
+    return ms, int(max_rows), VH_DT_NO_SIGNAL if norm is None else _NORM_SOURCES[norm]
+
+
+def table_metrics(rows, vox):
+    """What a reader wants of defect-table rows, in float64 from their integers alone: ``rows`` int64
+    [...][18], ``vox`` the voxel edges (mm) along rows, columns and slices.  A dict of arrays over the
+    leading axes, NaN for an unused row (column 0 = -1): ``volume_mL`` size * prod(vox / 10);
+    ``centroid`` [...][3] the index sums / size, in voxels, and ``centroid_mm`` = centroid * vox;
+    ``extent`` [...][3] max - min + 1 per axis; ``surface_mm2`` the voxel-face surface faces_r vox_c
+    vox_z + faces_c vox_r vox_z + faces_z vox_r vox_c; ``sphericity`` pi^(1/3) (6 volume_mm3)^(2/3) /
+    surface_mm2; ``mean``, ``min``, ``max`` of the normalised signal, sum_fx / 2^24 / n_sig, min_fx /
+    2^24, max_fx / 2^24, NaN where n_sig = 0."""
+    r = np.asarray(rows, dtype=np.int64)
+    if r.shape[-1:] != (VH_DT_COLS,):
+        raise ValueError(f"table_metrics: rows is [...][{VH_DT_COLS}], got shape {r.shape}")
+    v = np.asarray(vox, dtype=np.float64)
+    if v.shape != (3,):
+        raise ValueError(f"table_metrics: vox is three edges (mm), got {vox!r}")
+    f = r.astype(np.float64)
+    used = r[..., 0] >= 0
+    size = np.where(used, f[..., 1], np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        centroid = f[..., 2:5] / size[..., None]
+        extent = np.where(used[..., None], f[..., 6:11:2] - f[..., 5:10:2] + 1.0, np.nan)
+        surface = np.where(used, f[..., 11] * v[1] * v[2] + f[..., 12] * v[0] * v[2] + f[..., 13] * v[0] * v[1], np.nan)
+        sphericity = np.pi ** (1.0 / 3.0) * (6.0 * size * np.prod(v)) ** (2.0 / 3.0) / surface
+        n_sig = np.where(used & (r[..., 14] > 0), f[..., 14], np.nan)
+        mean = f[..., 15] / 16777216.0 / n_sig
+        lo = np.where(np.isnan(n_sig), np.nan, f[..., 16] / 16777216.0)
+        hi = np.where(np.isnan(n_sig), np.nan, f[..., 17] / 16777216.0)
+    return dict(volume_mL=size * np.prod(v / 10.0), centroid=centroid, centroid_mm=centroid * v, extent=extent,
+                surface_mm2=surface, sphericity=sphericity, mean=mean, min=lo, max=hi)
+
+
 def _denoise_args(sigma, n, strength, search, patch):
     """The per-study sigma as float32 [n] (a scalar is repeated) and the checked ints; ValueError for
     what the library would refuse, so the message names the argument."""
@@ -1671,6 +1722,28 @@ class Batch:
         self.ctx.check(self.L.vh_batch_download_components(self.h, _ptr(r), _ptr(sz), _ptr(counts), _ptr(stats)),
                        "vh_batch_download_components")
         return dict(root=r, size=sz, counts=counts, stats=stats, edges=e.copy())
+
+    def defect_table(self, min_size=1, max_rows=64, norm=None):
+        """Enqueue the defect table of every study (vh_batch_defect_table; the spec is in
+        include/vent_hip.h): one row per component of the last components() with at least ``min_size``
+        voxels (a scalar or one int per study), largest first, at most ``max_rows`` (1..1024).  ``norm``
+        'mean' | 'p99' fills the signal columns from the run's N4 (needs a run); None leaves them 0.
+        Read-only; download_defect_table fetches the last call's result."""
+        ms, max_rows, norm = _defect_table_args(min_size, max_rows, norm, self.shape[0])
+        self.ctx.check(self.L.vh_batch_defect_table(self.h, _ptr(ms), max_rows, norm), "vh_batch_defect_table")
+        self._dt = max_rows
+
+    def download_defect_table(self):
+        """The last defect_table() as a dict: ``rows`` int64 [B][max_rows][18] with the columns of
+        DT_COLUMNS (an unused row: -1, then zeros); ``stats`` int64 [B][4] = n_rows, n_qualifying, the
+        voxels in the rows, the voxels in the qualifying components; ``truncated`` bool [B], n_rows <
+        n_qualifying.  table_metrics() turns rows into mL, mm and signal means."""
+        B, n = self.shape[0], getattr(self, "_dt", 1)
+        rows = np.zeros((B, n, VH_DT_COLS), np.int64)
+        stats = np.zeros((B, 4), np.int64)
+        self.ctx.check(self.L.vh_batch_download_defect_table(self.h, _ptr(rows), _ptr(stats)),
+                       "vh_batch_download_defect_table")
+        return dict(rows=rows, stats=stats, truncated=stats[:, 0] < stats[:, 1])
 
     def zones(self, parts=(3, 1, 1), lateral=True, by="extent", labels=None, n_zones=None, norm="mean", bins=100,
               hi=1.5):

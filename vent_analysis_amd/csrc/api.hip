@@ -1442,6 +1442,56 @@ int vh_filter_components(vh_ctx *ctx, const uint8_t *a, int64_t R, int64_t C, in
     })
 }
 
+// ---- the defect table of a device-resident batch (defect_table.hip) ----------------------------------
+// Enqueue the table of the resident labelling.  It reads the root and size maps (and the run's N4) and
+// writes the table's buffers only, so nothing another call on the batch reads changes.
+static void batch_defect_table(vh_batch *b, const uint32_t *min_size, int32_t max_rows, int norm) {
+    if (!min_size) throw VhError{VH_ERR_ARG, "null min_size"};
+    if (max_rows < 1 || max_rows > VH_DT_MAX_ROWS) throw VhError{VH_ERR_ARG, "max_rows must be 1..1024"};
+    if (norm != VH_DT_NO_SIGNAL && norm != VH_NORM_MEAN && norm != VH_NORM_P99)
+        throw VhError{VH_ERR_ARG, "norm must be VH_NORM_MEAN, VH_NORM_P99 or VH_DT_NO_SIGNAL"};
+    for (int64_t i = 0; i < b->nb; ++i)
+        if (min_size[i] < 1) throw VhError{VH_ERR_ARG, "every min_size must be >= 1 (study " + std::to_string(i) + ")"};
+    if (norm != VH_DT_NO_SIGNAL) b->state.need_run();
+    b->state.need_components();
+    if (!vh_dt_takes(b)) throw VhError{VH_ERR_ARG, "defect table: more than 65535 studies or a volume of 2^31 voxels"};
+    const size_t nb = (size_t)b->nb;
+    b->d_dt_rows.reserve(nb * VH_DT_MAX_ROWS * VH_DT_COLS);   // the largest max_rows: no regrowth
+    b->d_dt_stats.reserve(nb * 4);
+    b->d_dt_keys.reserve(nb * VH_DT_MAX_ROWS);
+    b->d_dt_sel.reserve(nb * 2);
+    b->d_dt_cut.reserve(nb);
+    b->d_dt_hist.reserve(nb * 2048);
+    b->d_dt_cnt.reserve(nb);
+    b->d_dt_min.reserve(nb);
+    // (a pageable source: the copy has left min_size when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_dt_min, min_size, sizeof(uint32_t) * nb, hipMemcpyHostToDevice, b->stream));
+    vh_dt_launch(b, max_rows, norm);
+    b->state.defect_table_enqueued(max_rows, norm != VH_DT_NO_SIGNAL);
+}
+
+static void batch_download_defect_table(vh_batch *b, int64_t *rows, int64_t *stats) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the rows are copied as they are");
+    hipStream_t st = b->stream;
+    const size_t nb = (size_t)b->nb;
+    if (rows)
+        HIP_TRY(hipMemcpyAsync(rows, b->d_dt_rows, sizeof(int64_t) * nb * b->state.dt_rows() * VH_DT_COLS,
+                               hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, b->d_dt_stats, sizeof(int64_t) * nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+}
+
+int vh_batch_defect_table(vh_batch *b, const uint32_t *min_size, int32_t max_rows, int norm) {
+    BATCH_TRY(b, { batch_defect_table(b, min_size, max_rows, norm); })
+}
+
+int vh_batch_download_defect_table(vh_batch *b, int64_t *rows, int64_t *stats) {
+    BATCH_TRY(b, {
+        b->state.need_defect_table();
+        batch_download_defect_table(b, rows, stats);
+    })
+}
+
 // ---- the regional analysis of a device-resident batch (zones.hip) ------------------------------------
 // the argument checks (host only: nothing is enqueued before they pass); returns K
 static int32_t check_zones(const uint8_t *labels, int32_t n_zones, const int32_t *parts, int lateral, int by, int norm,

@@ -36,6 +36,9 @@ public:
         int32_t cr_bands = 0;        // its n_thr + 1 (while core_rind)
         bool components = false;     // vh_batch_components has been enqueued, and no filter has reused its buffers
         int32_t cc_classes = 0;      // its n_edges + 1 (while components)
+        bool defect_table = false;   // vh_batch_defect_table has been enqueued on that labelling
+        int32_t dt_rows = 0;         // its max_rows (while defect_table)
+        bool dt_signal = false;      // its norm was not VH_DT_NO_SIGNAL (while defect_table)
         bool zones = false;          // vh_batch_zones has been enqueued
         int32_t zone_k = 0;          // its K, the zones without zone 0 (while zones)
         int32_t zone_bins = 0;       // its n_bins (while zones)
@@ -58,9 +61,11 @@ public:
     void distribution_enqueued(int32_t bins) { f_.distribution = true; f_.dist_bins = bins; }
     void heterogeneity_enqueued(int32_t bins) { f_.heterogeneity = true; f_.het_bins = bins; }
     void core_rind_enqueued(int32_t bands) { f_.core_rind = true; f_.cr_bands = bands; }
-    void components_enqueued(int32_t classes) { f_.components = true; f_.cc_classes = classes; }
+    // (a new labelling, and the filter's, replace the maps the rows of a defect table refer to)
+    void components_enqueued(int32_t classes) { f_.components = true; f_.cc_classes = classes; f_.defect_table = false; }
+    void defect_table_enqueued(int32_t rows, bool signal) { f_.defect_table = true; f_.dt_rows = rows; f_.dt_signal = signal; }
     void zones_enqueued(int32_t k, int32_t bins) { f_.zones = true; f_.zone_k = k; f_.zone_bins = bins; }
-    void components_filtered() { f_.components = false; }   // vh_batch_filter_components relabelled into the same buffers
+    void components_filtered() { f_.components = f_.defect_table = false; }   // vh_batch_filter_components relabelled into the same buffers
     void proton_uploaded() { f_.proton = true; }
     void proton_src_uploaded() { f_.proton_src = true; }
 
@@ -89,6 +94,10 @@ public:
         need(f_.components, "vh_batch_components has not been called since the last run, the last edit of the inputs "
                             "or the last vh_batch_filter_components");
     }
+    void need_defect_table() const {
+        need(f_.defect_table, "vh_batch_defect_table has not been called since the last vh_batch_components, "
+                              "vh_batch_filter_components, run or edit of the inputs");
+    }
     void need_zones() const {
         need(f_.zones, "vh_batch_zones has not been called since the last run or the last edit of the inputs");
     }
@@ -113,6 +122,9 @@ public:
     int32_t cr_bands() const { return f_.cr_bands; }
     bool has_components() const { return f_.components; }
     int32_t cc_classes() const { return f_.cc_classes; }
+    bool has_defect_table() const { return f_.defect_table; }
+    int32_t dt_rows() const { return f_.dt_rows; }
+    bool dt_signal() const { return f_.dt_signal; }
     bool has_zones() const { return f_.zones; }
     int32_t zone_k() const { return f_.zone_k; }
     int32_t zone_bins() const { return f_.zone_bins; }
@@ -125,7 +137,7 @@ private:
     void clear_derived() {
         f_.labels = f_.selection = f_.ci_fresh = false;
         f_.layout = f_.overlay = f_.montage = f_.distribution = f_.heterogeneity = f_.core_rind = false;
-        f_.components = f_.zones = false;
+        f_.components = f_.defect_table = f_.zones = false;
     }
     static void need(bool ok, const char *msg) { if (!ok) throw VhError{VH_ERR_ARG, msg}; }
 };

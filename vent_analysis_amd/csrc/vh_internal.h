@@ -300,8 +300,17 @@ struct vh_batch {
     Buf<int32_t> d_cc_keep;          // [nb] its keep_largest
     Buf<unsigned long long> d_cc_picks;    // [nb][8] its picks: the k largest keys of each study, in order
     Buf<unsigned long long> d_cc_kept;     // [nb][2] the components and the voxels it kept
+    // vh_batch_defect_table (defect_table.hip): every buffer on first demand
+    Buf<unsigned long long> d_dt_rows;     // [nb][state.dt_rows()][VH_DT_COLS] the last call's rows (room for 1024 each)
+    Buf<unsigned long long> d_dt_stats;    // [nb][4] n_rows, n_qualifying, voxels in the rows, in the qualifying
+    Buf<unsigned long long> d_dt_keys;     // [nb][1024] the rows' keys (size << 32 | ~root), greatest first
+    Buf<unsigned long long> d_dt_sel;      // [nb][2] the radix select's prefix and remaining rank
+    Buf<unsigned long long> d_dt_cut;      // [nb] the cut-off key of a study with more components than rows (else 0)
+    Buf<uint32_t> d_dt_hist;         // [nb][2048] the digit histogram of one pass of the select
+    Buf<uint32_t> d_dt_cnt;          // [nb] the keys listed so far
+    Buf<uint32_t> d_dt_min;          // [nb] the last call's min_size
     // vh_batch_zones (zones.hip): every buffer on first demand
-    Buf<uint32_t> d_zn_prof;         // [nb][R + C + Z] the mask's on voxels of every row, column and slice
+    Buf<uint32_t> d_zn_prof;        // [nb][R + C + Z] the mask's on voxels of every row, column and slice
     Buf<uint8_t> d_zn_tab;           // [nb][R + C + Z] the part of every row, column (or its side) and slice
     Buf<int32_t> d_zn_geom;          // [nb][8] lo_r, hi_r, lo_c, hi_c, lo_z, hi_z, s, 0
     Buf<uint8_t> d_zn_map;           // [nb][V] the last call's zone maps
@@ -570,6 +579,13 @@ void vh_cc_launch(vh_batch *b, const uint8_t *src, int conn, const uint32_t *edg
                   uint32_t *size, unsigned long long *d_counts, unsigned long long *d_stats);
 void vh_cc_filter_launch(vh_batch *b, uint8_t *src, const int *root, const uint32_t *size, const uint32_t *d_min,
                          const int32_t *d_keep, int kmax, unsigned long long *d_picks, unsigned long long *d_kept);
+// defect_table.hip: the rows of the components in d_cc_root / d_cc_size with at least d_dt_min [nb]
+// voxels, at most max_rows (1..1024) a study, into d_dt_rows [nb][max_rows][VH_DT_COLS] and d_dt_stats
+// [nb][4]; norm VH_NORM_* reads the run's N4 and scalars for columns 14..17, VH_DT_NO_SIGNAL leaves them 0.
+// Every d_dt_* buffer is reserved by the caller (d_dt_min filled); the others are scratch, zeroed here.
+// vh_dt_takes: the grid fits
+bool vh_dt_takes(const vh_batch *b);
+void vh_dt_launch(vh_batch *b, int max_rows, int norm);
 // zones.hip: the zone maps (labels: d_zn_map holds the caller's bytes, else the rule of zones_host.h over
 // parts, lateral, by) into d_zn_map with the geometry in d_zn_geom, and the counts of the K + 1 zones over
 // the resident N4, mask, defect map, LB classes and zone map into d_zn_counts / d_zn_hist / d_zn_stats
