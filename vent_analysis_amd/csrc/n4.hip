@@ -868,6 +868,14 @@ __device__ float exact_min_block(const float *Uv, const uint32_t *colbits, const
     return m;
 }
 
+// The record of a level that has ended.  A study of fewer than two mask == 1 voxels has no fit (the
+// oracle refuses it; the volume-resident kernels run no iteration on it): the one pass the sweeps make
+// over nothing, whose convergence value is 0 / 0, is recorded as no iteration, like theirs.
+__device__ __forceinline__ void level_record(N4State &s, int level, double conv, int64_t n) {
+    s.iters_level[level] = n < 2 ? 0 : s.iters;
+    s.conv_level[level] = n < 2 ? 0.0f : (float)conv;
+}
+
 // Iteration control: convergence of the previous iteration, the while-condition of ITK's loop,
 // bin range (the else-if quirk: common case directly, the exact raster scan when the first masked
 // pixel is the strict minimum).  One block per volume.
@@ -900,8 +908,7 @@ __global__ void __launch_bounds__(VH_TPB) k_n4_ctrl(N4State *st, const double *p
             const bool go = conv_mode == 0 ? st[b].conv_w > thresh : conv > (double)thresh;
             if (!go) {
                 s.active = 0;
-                s.iters_level[level] = s.iters;
-                s.conv_level[level] = (float)conv;
+                level_record(s, level, conv, sc[b].n_mask1);
             }
         }
         if (s.active) {
@@ -941,8 +948,7 @@ __global__ void __launch_bounds__(64) k_n4_level_end(N4State *st, const double *
     if (threadIdx.x != 0) return;
     s.tlast ^= 1;
     s.conv = conv;
-    s.iters_level[level] = s.iters;
-    s.conv_level[level] = (float)conv;
+    level_record(s, level, conv, sc[b].n_mask1);
     s.active = 0;
 }
 
