@@ -220,16 +220,31 @@ __device__ __forceinline__ bool item_begin(Item &it, const uint64_t *rowmask, co
 }
 
 // Compact byte offset of (row x, this lane) or VH_OOB when the voxel is not in the mask; x is
-// wave-uniform and inside the item's slot.  With rr != nullptr also the voxel's raster rank (index
-// among the study's masked voxels in raster order: the order of ITK's convergence scan).
+// wave-uniform and inside the item's slot.  on: the lane's predicate "in the mask and valid".  The
+// row's mask is wave-uniform (an SGPR pair) and valid is too, so valid ? m : 0 *is* that predicate as
+// a lane mask: the selects that take it read the SGPR pair as their condition, no vector
+// instruction forms it.  (init_item and fit_item.)
+__device__ __forceinline__ uint32_t item_off(const Item &it, int x, bool valid, bool &on) {
+    const int xl = x - it.x0;
+    const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)it.mreg, xl);
+    const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(it.mreg >> 32), xl);
+    const uint64_t m = ((uint64_t)mhi << 32) | mlo;
+    const int r0 = __builtin_amdgcn_readlane(it.rsreg, xl);
+    const int below = lanes_below(m);
+    on = __builtin_amdgcn_inverse_ballot_w64(valid ? m : 0ull);
+    return on ? (uint32_t)(r0 + below) * 4u : VH_OOB;
+}
+// The form eval's walk keeps: the offset alone, the lane's own bit from two lane counts (bits 0..lane
+// minus bits below lane), and eval tests off != VH_OOB per voxel.  With the predicate above, eval's row
+// loops issue fewer instructions and k_n4_study runs longer (DESIGN_LOG.md).
+// With rr != nullptr also the voxel's raster rank (index among the study's masked voxels in raster
+// order: the order of ITK's convergence scan).
 __device__ __forceinline__ uint32_t item_off(const Item &it, int x, bool valid, int *rr = nullptr) {
     const int xl = x - it.x0;
     const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)it.mreg, xl);
     const uint32_t mhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(it.mreg >> 32), xl);
     const uint64_t m = ((uint64_t)mhi << 32) | mlo;
     const int r0 = __builtin_amdgcn_readlane(it.rsreg, xl);
-    // lane's own bit from two lane counts (bits 0..lane minus bits below lane): no per-lane
-    // (1 << lane) mask pair to keep in VGPRs across the row loops
     const int below = lanes_below(m);
     const bool on = valid && lanes_below(m >> 1) + (int)(m & 1ull) != below;
     if (rr) *rr = __builtin_amdgcn_readlane(it.rrreg, xl) + below;
@@ -465,12 +480,13 @@ __device__ void fit_item(const Item &it, const TabV &T, const double *Wk, const 
             // groups of FG rows, two per trip: the next group's U loads are in flight while this
             // group's rows are added (the chains still take the rows in order)
             uint32_t oA[FG], oB[FG];
+            bool nA[FG], nB[FG];   // the rows' lane predicates (item_off)
             float uA[FG], uB[FG];
-            auto issue = [&](int xb, uint32_t (&o)[FG], float (&u)[FG]) {
+            auto issue = [&](int xb, uint32_t (&o)[FG], bool (&on)[FG], float (&u)[FG]) {
 #pragma unroll
                 for (int g = 0; g < FG; ++g) {
                     const int xg = xb + g;
-                    o[g] = item_off(it, xg <= rb ? xg : rb, xg <= rb);
+                    o[g] = item_off(it, xg <= rb ? xg : rb, xg <= rb, on[g]);
 #ifdef AB_FIT_NOLOAD   // A/B builds only (fixed iteration counts): the fit without its U loads
                     if (MODE == 0) u[g] = 0.5f + 0.01f * (float)g;
 #else
@@ -478,40 +494,39 @@ __device__ void fit_item(const Item &it, const TabV &T, const double *Wk, const 
 #endif
                 }
             };
-            auto run = [&](int xb, const uint32_t (&o)[FG], const float (&u)[FG]) {
+            auto run = [&](int xb, const bool (&on)[FG], const float (&u)[FG]) {
 #pragma unroll
                 for (int g = 0; g < FG; ++g) {
                     // branch-free: a masked-out lane / row past the span adds exact zeros (its U load
                     // returned 0, so every operand is finite) -- see eval_item for why
-                    const bool on = o[g] != VH_OOB;
                     const int xg = xb + g <= rb ? xb + g : rb;
                     const double2 wa = Wx[2 * xg], wc = Wx[2 * xg + 1];
                     if (MODE == 0) {
                         const float rv = u[g] - sharpen_r(u[g], bmin, rinv, sE, bins, fbins, elast);
-                        const double p = on ? (double)rv * isyz : 0.0;
+                        const double p = on[g] ? (double)rv * isyz : 0.0;
                         acc0 = fma(wa.x, p, acc0);
                         acc1 = fma(wa.y, p, acc1);
                         acc2 = fma(wc.x, p, acc2);
                         acc3 = fma(wc.y, p, acc3);
                     } else {
-                        acc0 += on ? wa.x : 0.0;
-                        acc1 += on ? wa.y : 0.0;
-                        acc2 += on ? wc.x : 0.0;
-                        acc3 += on ? wc.y : 0.0;
+                        acc0 += on[g] ? wa.x : 0.0;
+                        acc1 += on[g] ? wa.y : 0.0;
+                        acc2 += on[g] ? wc.x : 0.0;
+                        acc3 += on[g] ? wc.y : 0.0;
                     }
                 }
             };
             if (x <= rb) {
-                issue(x, oA, uA);
+                issue(x, oA, nA, uA);
 #pragma unroll 1
                 for (int xb = x;; xb += 2 * FG) {
                     // the next group is issued unconditionally (rows past rb load nothing): a branch
                     // round the issue makes its loads maybe-pending at the join
-                    issue(xb + FG, oB, uB);
-                    run(xb, oA, uA);
+                    issue(xb + FG, oB, nB, uB);
+                    run(xb, nA, uA);
                     if (xb + FG > rb) break;
-                    issue(xb + 2 * FG, oA, uA);
-                    run(xb + FG, oB, uB);
+                    issue(xb + 2 * FG, oA, nA, uA);
+                    run(xb + FG, nB, uB);
                     if (xb + 2 * FG > rb) break;
                 }
             }

@@ -109,6 +109,7 @@ struct StudyMisc {
 #ifdef ST_PROF
     unsigned long long fprof[4];   // wave of thread st_pt: fit rows / push / contract / items
     unsigned long long eprof[9];   // thread st_pt: emap set-up, then slot / pointwise pass in turn
+    unsigned long long hprof[3];   // thread st_pt: hist zeroing, its value loop, (AB_HIST_DRY) a loop without atomics
 #endif
     double sd, sd2, conv;
     ChainState ch;             // PC's result (conv of the last iteration)
@@ -196,16 +197,17 @@ __device__ void init_item(const StudyArgs &a, int64_t b, const Item &it, int ite
 #pragma unroll 1
     for (int xb = it.xs; xb <= it.xe; xb += FIT_G) {
         uint32_t offs[FIT_G];
+        bool on[FIT_G];
         float iv[FIT_G];
 #pragma unroll
         for (int g = 0; g < FIT_G; ++g) {   // the group's image loads together
             const int xg = xb + g;
-            offs[g] = item_off(it, xg <= it.xe ? xg : it.xe, xg <= it.xe);
-            iv[g] = offs[g] != VH_OOB ? Ib[(int64_t)xg * a.CZ] : 0.0f;
+            offs[g] = item_off(it, xg <= it.xe ? xg : it.xe, xg <= it.xe, on[g]);
+            iv[g] = on[g] ? Ib[(int64_t)xg * a.CZ] : 0.0f;
         }
 #pragma unroll
         for (int g = 0; g < FIT_G; ++g) {
-            if (offs[g] == VH_OOB) continue;
+            if (!on[g]) continue;
             const float l = iv[g] > 0.0f ? (float)log((double)iv[g]) : 0.0f;
             st_store(rL, offs[g], l);
             st_store(rU, offs[g], l);
@@ -768,11 +770,30 @@ __device__ __forceinline__ EmapW emap_w(char *scr) {
 
 // hist (S3): compact U[j_begin, j_end) (j_begin a multiple of 16) into the packed LDS histogram
 // copies, 16 values per thread and trip, one 64-bit add per value
+// (hprof, profiling builds: thread 0 adds the cycles of the zeroing and of the value loop; AB_HIST_DRY
+// builds run the loop once more ahead of it with its loads and hist_pack but no atomic, hprof[2])
+template <bool DRY = false>
 __device__ __forceinline__ void hist_slice(const float *Ub, int64_t j_begin, int64_t j_end,
-                                           unsigned long long *Hc, float bmin, double rinv, int bins) {
+                                           unsigned long long *Hc, float bmin, double rinv, int bins,
+                                           unsigned long long *hprof = nullptr) {
     const int t = threadIdx.x;
+    unsigned long long hpc = hprof ? clock64() : 0ull, dry = 0ull;
+    auto hpm = [&](int k) {
+        if (hprof && t == 0) {
+            const unsigned long long c = clock64();
+            hprof[k] += c - hpc;
+            hpc = c;
+        }
+    };
+#ifdef AB_HIST_DRY
+    if (!DRY && hprof) {
+        hist_slice<true>(Ub, j_begin, j_end, Hc, bmin, rinv, bins);
+        hpm(2);
+    }
+#endif
     for (int i = t; i < ST_HC * VH_MAX_BINS; i += ST_TPB) Hc[i] = 0ull;
     __syncthreads();
+    hpm(0);
     unsigned long long *H = Hc + (t & (ST_HC - 1)) * VH_MAX_BINS;
     for (int64_t j0 = j_begin + (int64_t)t * 16; j0 < j_end; j0 += (int64_t)ST_TPB * 16) {
         float u[16];
@@ -790,10 +811,13 @@ __device__ __forceinline__ void hist_slice(const float *Ub, int64_t j_begin, int
         for (int k = 0; k < 16; ++k) {
             int idx;
             const unsigned long long w = hist_pack(u[k], bmin, rinv, bins, idx);
-            atomicAdd(&H[idx], w);
+            if (DRY) dry += w + (unsigned long long)idx;
+            else atomicAdd(&H[idx], w);
         }
     }
+    if (DRY && dry == 0x5a5a5a5a5a5a5a5aull) Hc[0] = dry;   // (keeps the dry loop's arithmetic)
     __syncthreads();
+    hpm(1);
 }
 
 // The Wiener kernel's Gaussian at point i of the padded series.  A function of its own, not inlined:
@@ -1068,6 +1092,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
     int st_nfirst = 0, st_nother = 0;   // evals of a level's first iteration (levels > 0) / all others
     if (t == 0) M.fprof[0] = M.fprof[1] = M.fprof[2] = M.fprof[3] = 0ull;
     if (t < 9) M.eprof[t] = 0ull;
+    if (t < 3) M.hprof[t] = 0ull;
 #endif
     int tpar = 0;   // Tg buffer of the last computed field's T windows
     for (int L = 0; L < a.nlev; ++L) {
@@ -1094,7 +1119,11 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
             ST_MARK(9);
             const float bmin = M.bin_min, slope = M.slope;
             const double rinv = 1.0 / (double)slope;   // div_r form of the bin division
+#ifdef ST_PROF
+            hist_slice(Ub, 0, n, EW.Hc, bmin, rinv, a.bins, M.hprof);
+#else
             hist_slice(Ub, 0, n, EW.Hc, bmin, rinv, a.bins);
+#endif
             ST_MARK(2);
             emap_phase(a, EW, sE, bmin, slope, [&](int h) {   // the four LDS copies' sums
                 unsigned long long s = 0ull;
@@ -1200,6 +1229,7 @@ __global__ void __launch_bounds__(ST_TPB, 4) k_n4_study(StudyArgs a) {
         printf("ST_PROF emap: setup %llu fwdVF %llu wiener %llu invV %llu clamp %llu fwdVD %llu product %llu "
                "invVD %llu divide %llu\n", M.eprof[0], M.eprof[1], M.eprof[2], M.eprof[3], M.eprof[4],
                M.eprof[5], M.eprof[6], M.eprof[7], M.eprof[8]);
+        printf("ST_PROF hist: zero %llu loop %llu dry %llu\n", M.hprof[0], M.hprof[1], M.hprof[2]);
         // (the eval figure above is the sum of the two below)
         printf("ST_PROF eval: first-of-level %llu in %d other %llu in %d\n", st_prof[11], st_nfirst,
                st_prof[6], st_nother);
