@@ -84,6 +84,12 @@
  *                a proton on its own grid (another matrix, pixel size or slice spacing) resampled onto the
  *                batch's by a separable anti-aliased linear filter, specified to the last bit
  *                (build-defined); kernel-timing class "resample_b", not listed
+ *   vh_batch_register_maps / vh_batch_download_register_maps_hist / vh_register_maps_pick /
+ *   vh_axis_candidates / vh_register_maps
+ *                the fine registration: a grid of candidate maps (scale x sub-voxel offset per axis) of
+ *                the resident source proton scored against the HPvent by mutual information, resampled,
+ *                coded and counted in one kernel (build-defined); kernel-timing class "register_maps_b",
+ *                not listed
  *   vh_pipe_*   the batch pipeline fed from host memory with overlapped transfers (build-defined)
  *   vh_comm_*    cohort histogram all-reduce over RCCL (build-defined, BASELINE config 4)
  */
@@ -975,9 +981,9 @@ int vh_segment(vh_ctx *ctx, const float *proton, int64_t R, int64_t C, int64_t Z
  * for the code pass, "segment_max_b" for the two maximum sweeps and "shift_b" (vh_batch_kernel_time reads
  * them; vh_batch_kernel_names does not list them).
  *
- * Not done here: a search over sub-voxel shifts, rotation, scaling, deformable registration.  (A proton
- * on another grid than the xenon's comes in through the resampling section below, which also applies a
- * sub-voxel offset.) */
+ * Not done here: rotation, deformable registration.  (A proton on another grid than the xenon's comes in
+ * through the resampling section below, which also applies a sub-voxel offset; the search over scale and
+ * sub-voxel offsets is the fine-registration section after it.) */
 #define VH_SHIFT_PROTON 0
 #define VH_SHIFT_MASK 1
 int vh_batch_register(vh_batch *b, const int32_t search[3], double *score /* [nb][ns] */, int32_t *best /* [nb][3] */,
@@ -1057,6 +1063,91 @@ int vh_batch_resample_proton(vh_batch *b, const double *map /* [nb][3][2] */);
 int vh_batch_download_proton_src(vh_batch *b, float *src);
 int vh_resample(vh_ctx *ctx, const float *src, const int64_t src_shape[3], int64_t R, int64_t C, int64_t Z,
                 int64_t batch, const double *map, float *out /* [batch][R][C][Z] */);
+
+/* ---- fine registration: a search over scale and sub-voxel offset of the resident source --------------
+ * The proton and the xenon are two breath-holds at two lung volumes: the lungs differ by a few per cent
+ * in size and by a fraction of a voxel in position, and on a 128-voxel axis 3 % of scale moves the lung
+ * edge by a voxel.  vh_batch_register_maps scores a grid of candidate resampling maps of the resident
+ * SOURCE proton (the resampling section above) against the resident HPvent by the mutual information of
+ * the register section, and returns the best map; vh_batch_resample_proton then applies it.  No resampled
+ * volume is written: the kernel resamples, codes and counts in one pass.  Every value is the resampler's
+ * to the last bit and every count an exact integer (tests/register_maps_ref.py is the same in numpy);
+ * only the score is floating point.
+ *
+ * Candidates.  count = (Kr, Kc, Kz) with 1 <= Kr, Kc <= 17 and 1 <= Kz <= 5, so nc = Kr Kc Kz <= 1445, the
+ * ceiling of the integer window.  axis_maps is double [nb][Kr + Kc + Kz][2]: per study the r list, then
+ * the c list, then the z list of (scale, offset), every entry within the resampler's limits (scale finite
+ * in [0.25, 4], offset finite with |offset| <= 2^20).  Candidate (kr, kc, kz) is the map
+ * (r[kr], c[kc], z[kz]) and has index
+ *   i = (kz Kr + kr) Kc + kc,
+ * the order of the shift index: z slowest, then r, then c.
+ *
+ * Value.  Q_i(v) is the destination value of the resampling section at voxel v under candidate i's map:
+ * the same tap tables (vh_resample_taps), the same nested float32 multiply-then-add order, no
+ * contraction -- bit for bit what vh_batch_resample_proton would write with that map.
+ *
+ * Counted voxels.  A destination voxel is skipped for candidate i when any of its three axes has tap count
+ * 0 there, i.e. it looks entirely outside the source.  This is the integer search's "both inside the
+ * volume": with a source of the batch's shape, scale 1 and integer offsets -S .. S the histograms are
+ * those of vh_batch_register's window (Sr, Sc, Sz) exactly, candidate (kr, kc, kz) being the shift
+ * (kr - Sr, kc - Sc, kz - Sz).
+ *
+ * Codes.  The xenon is coded as in the register section.  For the proton, smax is the maximum over F
+ * (finite and >= 0) of the study's whole resident source, scale = 256.0f / smax one float32 division, and
+ * code(Q) = min(255, (int)(Q * scale)) >> 3 with the product rounded to float32 (a product that is not
+ * below 255 gives 255 >> 3); Q is invalid when it is not finite or is < 0.  One scale per study keeps the
+ * codes independent of the candidate.  A study whose smax or xenon maximum is not > 0 is unregistrable:
+ * status 1, every score NaN, best = home, and its histograms are all zeros.
+ *
+ * Histogram and score.  J_i[a][b], uint32 [32][32], counts the counted voxels v with Q_i(v) and X(v) both
+ * valid, a the code of Q_i(v) and b the code of X(v); the counts are exact.  The score is the register
+ * section's mi of J_i, to its formula (vh_mi is the same on the host).
+ *
+ * Pick.  home = (hr, hc, hz) defaults to the middle entry (K - 1) / 2 of each list.  The largest score
+ * wins; among equal scores the smallest |kr - hr| + |kc - hc| + |kz - hz|, then the lowest index.  A NaN
+ * never wins; with nothing but NaN the pick is home.  vh_register_maps_pick is this for one study's
+ * scores [nc], on the host (home nullable); vh_batch_register_maps picks with it.
+ *
+ * Candidate lists.  vh_axis_candidates is a host function (no context, no device) that makes one axis's
+ * list around a base (scale0, offset0): factor f scales about the destination centre, then shift d, in
+ * destination voxels, moves.  With c = ((double)n_dst - 1.0) / 2.0, entry fi * ns + si of out [nf * ns][2]
+ * is
+ *   scale = scale0 * f,   offset = offset0 + scale0 * (c * (1.0 - f) + d),
+ * every operation a separately rounded double in that order.  VH_ERR_ARG, with nothing written, for a
+ * null pointer, nf or ns < 1, n_dst outside 1..2^20 or a result outside the resampler's limits.
+ *
+ * vh_batch_register_maps needs a resident source, waits, and returns score [nb][nc], best [nb][3] (the
+ * picked kr, kc, kz) and, when asked for, best_map [nb][3][2] (the picked list entries as they were
+ * given, ready for vh_batch_resample_proton), best_score [nb] and status [nb] (0, or 1: unregistrable).
+ * It changes nothing another call reads: the resident source, proton, HPvent, mask and a run's results
+ * stay as they are.  Its device buffers are allocated on the first call and grow: nb * nc * 4 KiB of
+ * histograms, a byte volume of xenon codes and the nb * (Kr + Kc + Kz) tap tables.
+ * vh_batch_download_register_maps_hist waits and returns the last call's histograms [nb][nc][32][32].
+ * vh_register_maps is the host-buffer form on the context's scratch batch; best_map and status are
+ * nullable.
+ *
+ * VH_ERR_ARG, with nothing enqueued or changed: a null batch or a null required pointer, no resident
+ * source, a count outside its limits, a list entry outside its limits or not finite, home outside its
+ * list, vh_batch_download_register_maps_hist before any vh_batch_register_maps call (and a batch of more
+ * than 65535 studies or with a dimension above 2^20).  Every other batch and source shape the resampler
+ * takes is taken, by the one fused kernel.  The kernel-timing classes are "register_maps_b" for the fused
+ * kernel, "register_maps_codes_b" for the xenon codes, "segment_max_b" for the two maximum sweeps and
+ * "register_score_b" for the scores (vh_batch_kernel_time reads them; vh_batch_kernel_names does not list
+ * them).
+ *
+ * Not done here: rotation, shear, deformable registration; an optimiser (the caller repeats the search on
+ * a finer list around best_map); masks resampled from another grid. */
+int vh_batch_register_maps(vh_batch *b, const int32_t count[3], const double *axis_maps /* [nb][Kr+Kc+Kz][2] */,
+                           const int32_t *home /* [3], nullable */, double *score /* [nb][nc] */,
+                           int32_t *best /* [nb][3] */, double *best_map /* [nb][3][2], nullable */,
+                           double *best_score /* [nb], nullable */, int32_t *status /* [nb], nullable */);
+int vh_batch_download_register_maps_hist(vh_batch *b, uint32_t *hist /* [nb][nc][32][32] */);
+int vh_register_maps_pick(const double *score, const int32_t count[3], const int32_t home[3], int32_t best[3]);
+int vh_axis_candidates(double scale0, double offset0, int64_t n_dst, const double *factors, int32_t nf,
+                       const double *shifts, int32_t ns, double *out /* [nf * ns][2] */);
+int vh_register_maps(vh_ctx *ctx, const float *src, const int64_t src_shape[3], const float *hp, int64_t R, int64_t C,
+                     int64_t Z, int64_t batch, const int32_t count[3], const double *axis_maps, const int32_t *home,
+                     double *score, int32_t *best, double *best_map, int32_t *status);
 
 /* ---- TWIX raw reconstruction --------------------------------------- */
 /* process_RAW's image from raw k-space (Vent_Analysis.py:537-540): for every slice k,

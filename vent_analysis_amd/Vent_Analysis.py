@@ -572,6 +572,45 @@ class Vent_Analysis:
         self.proton = _lib.resample(np.asarray(p, dtype=np.float32), np.shape(self.HPvent), m, device=self.device)[0]
         return self.proton
 
+    def align_proton(self, proton_vox=None, search=(4, 4, 1), factors=_lib.RM_FACTORS, shifts=_lib.RM_SHIFTS,
+                     zshifts=_lib.RM_SHIFTS, apply=True):
+        """Align ``self.proton``, on its own grid, to ``self.HPvent`` in scale and sub-voxel position
+        (build-defined), on the GPU.  In order: the centre-on-centre map of the two grids (_lib.grid_map);
+        a resampling with it; the integer registration of register_proton over ``search``; its shift folded
+        into the map; the fine registration around that map (_lib.register_maps: every candidate of
+        ``factors`` x ``shifts`` on the rows and on the columns and of ``zshifts`` on the slices, scored by
+        the mutual information of its resampling -- the spec is in include/vent_hip.h); and a final
+        resampling with the best map.  ``proton_vox`` is as in resample_proton.  Returns (best_map float64
+        [3][2], mi).  With ``apply`` ``self.proton`` becomes the aligned float32 array of HPvent's shape;
+        nothing else is changed."""
+        p = self.proton
+        if isinstance(p, str) or np.ndim(p) != 3:
+            raise ValueError("align_proton: self.proton must be a 3-D array")
+        if np.ndim(self.HPvent) != 3:
+            raise ValueError("align_proton: self.HPvent must be a 3-D array")
+        if isinstance(self.vox, str):
+            raise ValueError("align_proton: self.vox is not set")
+        if proton_vox is None:
+            ds = getattr(self, 'proton_ds', None)
+            if ds is None or isinstance(ds, str):
+                raise ValueError("align_proton: pass proton_vox (there is no proton DICOM header to read it from)")
+            proton_vox = ingest.header_vox(ds)
+        shape = np.shape(self.HPvent)
+        src = np.asarray(p, dtype=np.float32)
+        hp = np.asarray(self.HPvent, dtype=np.float32)
+        se = _lib._register_args(search, shape)
+        m0 = _lib.grid_map(src.shape, proton_vox, shape, self.vox)
+        _lib._resample_args(m0, 1, src.shape)
+        coarse = _lib.resample(src, shape, m0, device=self.device)[0]
+        shift, _, _ = _lib.register(coarse, hp, se, device=self.device)
+        m1 = _lib.grid_map(src.shape, proton_vox, shape, self.vox, tuple(int(v) for v in shift[0]))
+        lists, home = _lib.map_candidates(m1, shape, factors, shifts, zshifts=zshifts)
+        best, best_map, score, _ = _lib.register_maps(src, hp, lists, home, device=self.device)
+        kr, kc, kz = (int(v) for v in best[0])
+        if apply:
+            self.proton = _lib.resample(src, shape, best_map[0], device=self.device)[0]
+        return best_map[0], float(score[0][kz, kr, kc])
+
     @staticmethod
     def _snr_dtype(v, A):
         dt = np.asarray(A).dtype

@@ -287,6 +287,122 @@ def _resample_args(maps, n, src_shape=None):
     return m
 
 
+RM_MAX_COUNT = (17, 17, 5)                  # vh_batch_register_maps: the most candidates of the r, c and z lists
+RM_FACTORS = (0.94, 0.97, 1.0, 1.03, 1.06)  # map_candidates: the scale factors of the in-plane axes
+RM_SHIFTS = (-0.5, 0.0, 0.5)                # ... and the shifts of every axis, in destination voxels
+
+
+def axis_candidates(base, n_dst, factors, shifts):
+    """The candidate list of one axis for register_maps (vh_axis_candidates, on the host: no device; the
+    spec is in include/vent_hip.h): around ``base`` (scale0, offset0), factor f scales about the centre of
+    the ``n_dst`` destination voxels and shift d, in destination voxels, moves.  Entry fi * len(shifts) + si is
+    scale = scale0 * f, offset = offset0 + scale0 * ((n_dst - 1) / 2 * (1 - f) + d).  Returns float64
+    [len(factors) * len(shifts)][2]; ValueError for an empty list or a result outside the resampler's limits."""
+    b = _real_array(base, "axis_candidates: base")
+    f = np.ascontiguousarray(_real_array(factors, "axis_candidates: factors"))
+    d = np.ascontiguousarray(_real_array(shifts, "axis_candidates: shifts"))
+    if b.shape != (2,) or f.ndim != 1 or d.ndim != 1 or not f.size or not d.size:
+        raise ValueError("axis_candidates: base is (scale, offset), factors and shifts are non-empty 1-D lists")
+    out = np.zeros((f.size * d.size, 2), np.float64)
+    rc = lib().vh_axis_candidates(float(b[0]), float(b[1]), int(n_dst), _ptr(f), f.size, _ptr(d), d.size, _ptr(out))
+    if rc != VH_OK:
+        raise ValueError(f"axis_candidates: n_dst 1..2^20 and every candidate's scale in {list(RESAMPLE_SCALE)}, "
+                         f"|offset| <= 2^20, got base {base!r}, n_dst {n_dst!r}, factors {factors!r}, shifts {shifts!r}")
+    return out
+
+
+def _home_of(values, one):
+    v = np.asarray(values, np.float64)
+    at = np.flatnonzero(v == one)
+    return int(at[0]) if at.size else None
+
+
+def map_candidates(base_map, dst_shape, factors=RM_FACTORS, shifts=RM_SHIFTS, zfactors=(1.0,), zshifts=RM_SHIFTS):
+    """The three candidate lists of register_maps around one map [3][2] (grid_map makes one): the r and the
+    c axis take ``factors`` x ``shifts``, the z axis ``zfactors`` x ``zshifts`` (axis_candidates).  Returns
+    (lists, home): lists the r, c and z list, float64 [K][2] each; home the entry of each list that is the
+    base itself (factor 1.0 and shift 0.0), or the middle entry where a list has none."""
+    m = _real_array(base_map, "map_candidates: base_map")
+    if m.shape != (3, 2):
+        raise ValueError(f"map_candidates: base_map is [3][2], got shape {m.shape}")
+    n = _shape3(dst_shape, "map_candidates: dst_shape")
+    lists, home = [], []
+    for a in range(3):
+        fa, sa = (zfactors, zshifts) if a == 2 else (factors, shifts)
+        lists.append(axis_candidates(m[a], n[a], fa, sa))
+        fi, si = _home_of(fa, 1.0), _home_of(sa, 0.0)
+        home.append(fi * len(sa) + si if fi is not None and si is not None else (len(lists[-1]) - 1) // 2)
+    return lists, tuple(home)
+
+
+def _register_maps_args(lists, n, home=None):
+    """(count int32 [3], axis_maps float64 [n][Kr+Kc+Kz][2] contiguous, home int32 [3] or None) for
+    vh_batch_register_maps: ``lists`` is the r, the c and the z list, each [K][2] of (scale, offset) for
+    every study or [n][K][2], one per study; 1 <= Kr, Kc <= 17, 1 <= Kz <= 5; every scale finite in
+    [0.25, 4] and every offset finite with |offset| <= 2^20; ``home`` three ints inside the lists.
+    ValueError for what the library would refuse, so the message names the argument."""
+    if isinstance(lists, np.ndarray) or len(lists) != 3:
+        raise ValueError("register_maps: lists is the r, the c and the z list")
+    parts = []
+    for a, (l, hi) in enumerate(zip(lists, RM_MAX_COUNT)):
+        m = _real_array(l, f"register_maps: lists[{a}]")
+        if m.ndim == 2:
+            m = np.broadcast_to(m, (n,) + m.shape)
+        if m.ndim != 3 or m.shape[0] != n or m.shape[2] != 2:
+            raise ValueError(f"register_maps: lists[{a}] is [K][2] or [{n}][K][2], got shape {np.shape(l)}")
+        if not 1 <= m.shape[1] <= hi:
+            raise ValueError(f"register_maps: lists[{a}] has 1..{hi} candidates, got {m.shape[1]}")
+        parts.append(m)
+    am = np.ascontiguousarray(np.concatenate(parts, axis=1))
+    s, o = am[..., 0], am[..., 1]
+    with np.errstate(invalid="ignore"):
+        ok = (s >= RESAMPLE_SCALE[0]) & (s <= RESAMPLE_SCALE[1]) & (np.abs(o) <= RESAMPLE_MAX_OFFSET)
+    if not ok.all():
+        raise ValueError(f"register_maps: every scale in {list(RESAMPLE_SCALE)} and every |offset| <= 2^20, both finite "
+                         f"(studies {sorted(set(np.argwhere(~ok)[:, 0].tolist()))})")
+    count = np.asarray([q.shape[1] for q in parts], np.int32)
+    return count, am, _home_args(home, count)
+
+
+def _home_args(home, count):
+    if home is None:
+        return None
+    h = np.asarray(home)
+    if h.dtype == np.bool_ or not np.issubdtype(h.dtype, np.integer) or h.shape != (3,):
+        raise ValueError(f"register_maps: home is three ints, got {home!r}")
+    if (h < 0).any() or (h >= np.asarray(count)).any():
+        raise ValueError(f"register_maps: home must lie inside the lists of {tuple(int(v) for v in count)} "
+                         f"candidates, got {home!r}")
+    return np.ascontiguousarray(h, dtype=np.int32)
+
+
+def register_maps_pick(score, home=None, count=None):
+    """The best candidate (kr, kc, kz) of one study's scores (vh_register_maps_pick, on the host): the
+    largest score, among equal scores the smallest |kr - hr| + |kc - hc| + |kz - hz|, then the lowest
+    index; a NaN never wins.  ``score`` is [Kz][Kr][Kc], or flat in that order with ``count`` (Kr, Kc, Kz);
+    ``home`` defaults to the middle entry of each list."""
+    sc = np.ascontiguousarray(score, dtype=np.float64)
+    if count is None:
+        if sc.ndim != 3:
+            raise ValueError("register_maps_pick: score is [Kz][Kr][Kc], or flat with count")
+        count = (sc.shape[1], sc.shape[2], sc.shape[0])
+    c = np.asarray(count)
+    if c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer) or c.shape != (3,):
+        raise ValueError(f"register_maps_pick: count is three ints, got {count!r}")
+    if (c < 1).any() or (c > np.asarray(RM_MAX_COUNT)).any():
+        raise ValueError(f"register_maps_pick: count must be 1..17, 1..17, 1..5, got {count!r}")
+    cn = np.ascontiguousarray(c, dtype=np.int32)
+    if sc.size != int(np.prod(cn)):
+        raise ValueError(f"register_maps_pick: count {tuple(cn.tolist())} has {int(np.prod(cn))} candidates, got "
+                         f"{sc.size} scores")
+    h = _home_args(home, cn)
+    best = np.zeros(3, np.int32)
+    rc = lib().vh_register_maps_pick(_ptr(sc), _ptr(cn), _ptr(h), _ptr(best))
+    if rc != VH_OK:
+        raise ValueError(f"vh_register_maps_pick: status {rc}")
+    return tuple(int(v) for v in best)
+
+
 def denoise_constants(sigma, strength=2.0, patch=1):
     """(inv_h2, bias) float32 of one study as vh_batch_denoise forms them: in double from the float32
     sigma and strength, rounded once.  inv_h2 = 1 / (2 n (k sigma)^2), n = (2 patch + 1)^2; bias =
@@ -429,6 +545,11 @@ _SIGS = {
     "vh_batch_resample_proton": ([_P, _P], ct.c_int),
     "vh_batch_download_proton_src": ([_P, _P], ct.c_int),
     "vh_resample": ([_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P], ct.c_int),
+    "vh_batch_register_maps": ([_P, _P, _P, _P, _P, _P, _P, _P, _P], ct.c_int),
+    "vh_batch_download_register_maps_hist": ([_P, _P], ct.c_int),
+    "vh_register_maps_pick": ([_P, _P, _P, _P], ct.c_int),
+    "vh_axis_candidates": ([ct.c_double, ct.c_double, _I64, _P, ct.c_int32, _P, ct.c_int32, _P], ct.c_int),
+    "vh_register_maps": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P], ct.c_int),
     "vh_recon": ([_P, _P, _I64, _I64, _I64, _P], ct.c_int),
     "vh_pipe_create": ([_P, _I64, _I64, _I64, _I64, ct.c_int, ct.POINTER(_P)], ct.c_int),
     "vh_pipe_run": ([_P, _P, _P, _I64, ct.POINTER(RunOpts), _P, _P, _P, _P, _P], ct.c_int),
@@ -1303,6 +1424,28 @@ def resample(src, dst_shape, maps, device=0):
     return out
 
 
+def register_maps(src, hp, lists, home=None, device=0):
+    """The fine registration from host arrays (vh_register_maps; the spec is in include/vent_hip.h): ``src``
+    the protons on their own grid, a 3-D volume or a 4-D batch of one shape, ``hp`` the xenon volumes,
+    ``lists`` the r, c and z candidate lists of (scale, offset) (map_candidates makes them).  Returns (best
+    int32 [B][3], best_map float64 [B][3][2], score float64 [B][Kz][Kr][Kc], status int32 [B])."""
+    s = as_batch(src, np.float32)
+    x = as_batch(hp, np.float32)
+    if s.shape[0] != x.shape[0]:
+        raise ValueError(f"register_maps: {s.shape[0]} sources and {x.shape[0]} xenon volumes")
+    B, R, C, Z = x.shape
+    shape = np.asarray(_shape3(s.shape[1:], "register_maps: the source shape", RESAMPLE_MAX_SRC), np.int64)
+    count, am, h = _register_maps_args(lists, B, home)   # (before any device call)
+    c = context(device)
+    score = np.zeros((B, int(count[2]), int(count[0]), int(count[1])), np.float64)
+    best = np.zeros((B, 3), np.int32)
+    best_map = np.zeros((B, 3, 2), np.float64)
+    status = np.zeros(B, np.int32)
+    c.check(c.L.vh_register_maps(c.h, _ptr(s), _ptr(shape), _ptr(x), R, C, Z, B, _ptr(count), _ptr(am), _ptr(h),
+                                 _ptr(score), _ptr(best), _ptr(best_map), _ptr(status)), "vh_register_maps")
+    return best, best_map, score, status
+
+
 def ci(defect, table, minvox, device=0, shell=True, out=None):
     """table: vent_analysis_amd.sphere.SphereTable for this shape (kept in HBM per context after
     the first call).  Returns (ci f64, scalar[B], shell int32 or None).  The map goes into a pooled
@@ -1975,6 +2118,30 @@ class Batch:
         out = np.empty(shape, np.float32)
         self.ctx.check(self.L.vh_batch_download_proton_src(self.h, _ptr(out)), "vh_batch_download_proton_src")
         return out
+
+    def register_maps(self, lists, home=None, hist=False):
+        """Score a grid of candidate maps of the resident source proton against the resident HPvent by
+        mutual information (vh_batch_register_maps; the spec is in include/vent_hip.h) and wait.  ``lists``
+        is the r, the c and the z list of (scale, offset), each [K][2] for every study or [B][K][2]
+        (map_candidates makes them); ``home`` the candidate ties fall to, the middle entries by default.
+        Returns (best int32 [B][3] the picked (kr, kc, kz), best_map float64 [B][3][2] ready for
+        resample_proton, score float64 [B][Kz][Kr][Kc], status int32 [B]: 1 where a study has no voxel > 0
+        in one of the images, its scores NaN and its pick home); with ``hist`` also the joint histograms
+        uint32 [B][Kz][Kr][Kc][32][32].  Changes nothing another call reads."""
+        n = self.shape[0]
+        count, am, h = _register_maps_args(lists, n, home)   # (before any device call)
+        score = np.zeros((n, int(count[2]), int(count[0]), int(count[1])), np.float64)
+        best = np.zeros((n, 3), np.int32)
+        best_map = np.zeros((n, 3, 2), np.float64)
+        status = np.zeros(n, np.int32)
+        self.ctx.check(self.L.vh_batch_register_maps(self.h, _ptr(count), _ptr(am), _ptr(h), _ptr(score), _ptr(best),
+                                                     _ptr(best_map), None, _ptr(status)), "vh_batch_register_maps")
+        if not hist:
+            return best, best_map, score, status
+        hh = np.zeros(score.shape + (REG_LEVELS, REG_LEVELS), np.uint32)
+        self.ctx.check(self.L.vh_batch_download_register_maps_hist(self.h, _ptr(hh)),
+                       "vh_batch_download_register_maps_hist")
+        return best, best_map, score, status, hh
 
     def cohort_hist(self):
         h = np.zeros(COHORT_BINS, np.uint64)

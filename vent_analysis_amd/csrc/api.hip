@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "vh_internal.h"
+#include "register_maps_host.h"
 #include "resample_host.h"
 #include "zones_host.h"
 
@@ -2294,6 +2295,124 @@ int vh_resample(vh_ctx *ctx, const float *src, const int64_t src_shape[3], int64
         batch_upload_proton_src(b, src, src_shape);
         batch_resample_proton(b, map);
         d2h_on_stream(b, out, b->d_proton, sizeof(float) * (size_t)batch * b->V);
+    })
+}
+
+// ---- the fine registration of a device-resident batch (register_maps.hip) -------------------------
+// The candidate list of one axis and the pick, on the host alone (register_maps_host.h).
+int vh_axis_candidates(double scale0, double offset0, int64_t n_dst, const double *factors, int32_t nf,
+                       const double *shifts, int32_t ns, double *out) {
+    return rm_axis_candidates(scale0, offset0, n_dst, factors, nf, shifts, ns, out) ? VH_OK : VH_ERR_ARG;
+}
+
+int vh_register_maps_pick(const double *score, const int32_t count[3], const int32_t home[3], int32_t best[3]) {
+    return rm_pick(score, count, home, best) ? VH_OK : VH_ERR_ARG;
+}
+
+// the argument checks of a fine registration (host only: nothing is enqueued before they pass)
+static void check_register_maps(const int32_t *count, const double *axis_maps, const int32_t *home, int64_t nb) {
+    if (!rm_count_in_limits(count)) throw VhError{VH_ERR_ARG, "count must be 1..17, 1..17, 1..5"};
+    if (!axis_maps) throw VhError{VH_ERR_ARG, "null axis_maps"};
+    if (!rm_home_in_lists(count, home)) throw VhError{VH_ERR_ARG, "home must lie inside its lists"};
+    const int64_t n = (int64_t)count[0] + count[1] + count[2];
+    for (int64_t i = 0; i < nb; ++i)
+        for (int64_t k = 0; k < n; ++k)
+            if (!rs_map_in_limits(axis_maps[2 * (i * n + k)], axis_maps[2 * (i * n + k) + 1]))
+                throw VhError{VH_ERR_ARG, "every scale must be in [0.25, 4] and every |offset| <= 2^20, both finite (study " +
+                                              std::to_string(i) + ")"};
+}
+
+// The tables of every list entry on the host, their upload, the maxima, the xenon codes, the joint
+// histogram of every candidate and the scores of d_proton_src against d_hp, then on the host the pick of
+// every study; waits.  It writes its own buffers only.
+static void batch_register_maps(vh_batch *b, const int32_t *count, const double *axis_maps, const int32_t *home,
+                                double *score, int32_t *best, double *best_map, double *best_score,
+                                int32_t *status) {
+    need_proton_src(b);
+    const int64_t dim[3] = {b->R, b->C, b->Z};
+    const int64_t nl = (int64_t)count[0] + count[1] + count[2];
+    const int64_t stride = 10 * (count[0] * b->R + count[1] * b->C + count[2] * b->Z);
+    std::vector<int32_t> tab((size_t)(b->nb * stride));
+    for (int64_t q = 0; q < b->nb; ++q) {
+        int32_t *t = tab.data() + q * stride;
+        const double *m = axis_maps + 2 * q * nl;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t n = dim[a];
+            for (int k = 0; k < count[a]; ++k, m += 2, t += 10 * n)
+                if (!rs_axis_taps(b->rs_shape[a], n, m[0], m[1], t, t + n, reinterpret_cast<float *>(t + 2 * n)))
+                    throw VhError{VH_ERR_ARG, "register_maps: a dimension of the batch is above 2^20"};
+        }
+    }
+    RmPlan plan;
+    if (!vh_register_maps_plan(b, b->rs_shape, count, tab.data(), plan))
+        throw VhError{VH_ERR_ARG, "register_maps: batch or tile count out of range"};
+    const size_t nb = (size_t)b->nb, nc = (size_t)count[0] * count[1] * count[2];
+    b->d_rm_max.reserve(2 * nb);
+    b->d_rm_cx.reserve(nb * (size_t)b->V);
+    b->d_rm_tab.reserve(tab.size());
+    b->d_rm_score.reserve(nb * nc);
+    b->rm_nc = 0;   // (a failed growth leaves no histograms to download)
+    b->d_rm_hist.reserve(nb * nc * 1024);
+    // (pageable source: the copy has left tab when the call returns)
+    HIP_TRY(hipMemcpyAsync(b->d_rm_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, b->stream));
+    vh_register_maps_launch(b, plan, b->d_proton_src, b->d_hp, b->d_rm_tab, b->d_rm_max, b->d_rm_cx, b->d_rm_hist,
+                            b->d_rm_score);
+    b->rm_nc = (int64_t)nc;
+    std::vector<uint32_t> bits(2 * nb);
+    HIP_TRY(hipMemcpyAsync(bits.data(), b->d_rm_max, sizeof(uint32_t) * 2 * nb, hipMemcpyDeviceToHost, b->stream));
+    d2h_on_stream(b, score, b->d_rm_score, sizeof(double) * nb * nc);
+    for (size_t i = 0; i < nb; ++i) {
+        float sm, xm;
+        memcpy(&sm, &bits[i], sizeof(float));
+        memcpy(&xm, &bits[nb + i], sizeof(float));
+        int32_t *at = best + 3 * i;
+        (void)rm_pick(score + nc * i, count, home, at);
+        if (status) status[i] = (sm > 0.0f && xm > 0.0f) ? 0 : 1;
+        if (best_map) {
+            const double *m = axis_maps + 2 * (int64_t)i * nl;
+            const int64_t off[3] = {at[0], count[0] + at[1], count[0] + count[1] + at[2]};
+            for (int a = 0; a < 3; ++a) {
+                best_map[6 * i + 2 * a] = m[2 * off[a]];
+                best_map[6 * i + 2 * a + 1] = m[2 * off[a] + 1];
+            }
+        }
+        if (best_score)
+            best_score[i] = score[nc * i + ((size_t)at[2] * count[0] + (size_t)at[0]) * count[1] + (size_t)at[1]];
+    }
+}
+
+int vh_batch_register_maps(vh_batch *b, const int32_t count[3], const double *axis_maps, const int32_t *home,
+                           double *score, int32_t *best, double *best_map, double *best_score, int32_t *status) {
+    BATCH_TRY(b, {
+        if (!score || !best) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_register_maps(count, axis_maps, home, b->nb);
+        batch_register_maps(b, count, axis_maps, home, score, best, best_map, best_score, status);
+    })
+}
+
+int vh_batch_download_register_maps_hist(vh_batch *b, uint32_t *hist) {
+    BATCH_TRY(b, {
+        if (!hist) throw VhError{VH_ERR_ARG, "null buffer"};
+        if (b->rm_nc <= 0) throw VhError{VH_ERR_ARG, "vh_batch_register_maps has not been called"};
+        d2h_on_stream(b, hist, b->d_rm_hist, sizeof(uint32_t) * (size_t)b->nb * (size_t)b->rm_nc * 1024);
+    })
+}
+
+int vh_register_maps(vh_ctx *ctx, const float *src, const int64_t src_shape[3], const float *hp, int64_t R, int64_t C,
+                     int64_t Z, int64_t batch, const int32_t count[3], const double *axis_maps, const int32_t *home,
+                     double *score, int32_t *best, double *best_map, int32_t *status) {
+    if (!ctx) return VH_ERR_ARG;
+    API_TRY(ctx, {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (!src || !hp || !score || !best) throw VhError{VH_ERR_ARG, "null buffer"};
+        check_dims(R, C, Z, batch);
+        check_resample_shape(src_shape);
+        check_register_maps(count, axis_maps, home, batch);
+        vh_batch *b = scratch_batch(ctx, R, C, Z, batch);
+        b->profile = ctx->profile != 0;
+        batch_upload(b, hp, nullptr);
+        batch_upload_proton_src(b, src, src_shape);
+        batch_register_maps(b, count, axis_maps, home, score, best, best_map, nullptr, status);
     })
 }
 

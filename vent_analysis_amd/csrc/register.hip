@@ -8,8 +8,6 @@
 #include "vh_internal.h"
 
 #define RG_TPB 256
-#define RG_INVALID 255u
-#define RG_BINS 1024                // 32 x 32
 #define RG_NW 8                     // waves of a joint-histogram workgroup: a shift each per round
 #define RG_NC 2                     // copies of a wave's histogram: lane l counts in copy l % RG_NC
 #define RG_HP 1025                  // words between the copies: the copies of a bin lie on different banks
@@ -17,18 +15,7 @@
 #define RG_LDS_MAX (156 * 1024)     // histograms and both code tiles: inside the CU's 160 KiB
 #define RG_LDS_PLAIN (64 * 1024)    // above it the launch needs MaxDynamicSharedMemorySize
 
-// ---- codes ----------------------------------------------------------------------------------------
-// in F: finite and >= 0 (NaN fails both comparisons; -0.0 is in F and counts as +0.0), as segment.hip
-__device__ __forceinline__ bool rg_in_f(float x) { return x >= 0.0f && x <= 3.402823466e+38f; }
-
-// min(255, (int)(x * scale)) >> 3, the product rounded to float32 (one that is not below 255 -- NaN from
-// an infinite scale times zero included -- is bin 255, as in k_seg_hist); 255 outside F
-__device__ __forceinline__ uint32_t rg_code(float x, float scale) {
-    if (!rg_in_f(x)) return RG_INVALID;
-    const float p = __fmul_rn(x, scale);
-    return (uint32_t)(p < 255.0f ? (int)p : 255) >> 3;
-}
-
+// ---- codes (rg_in_f, rg_code, RG_INVALID: vh_internal.h, shared with register_maps.hip) ----------------
 // cp / cx [nb][V] = the codes of the proton and of the HPvent; maxb [2][nb] the bit patterns of their
 // maxima over F (k_seg_max).  A study whose maximum is not > 0 is unregistrable: its codes are never
 // read, and are written as invalid.  grid (blocks, nb)

@@ -84,13 +84,14 @@ __global__ void __launch_bounds__(SG_TPB) k_seg_hist(const float *__restrict__ x
 }
 
 // the maximum sweep alone (d_max_bits zeroed by the caller): the registration takes it for both images
-void vh_seg_max_launch(vh_batch *b, const float *x, uint32_t *d_max_bits) {
+void vh_seg_max_launch_n(vh_batch *b, const float *x, int64_t n, uint32_t *d_max_bits) {
     if (b->nb > 65535) throw VhError{VH_ERR_ARG, "more than 65535 studies"};   // (grid y)
-    const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((b->V + SG_TPB * 128 - 1) / (SG_TPB * 128), 32));
-    ScopedKTimer tm(b, "segment_max_b", 4.0 * (double)b->nb * (double)b->V, true);
-    k_seg_max<<<dim3((unsigned)chunks, (unsigned)b->nb, 1), SG_TPB, 0, b->stream>>>(x, b->V, d_max_bits, tm.stamp());
+    const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((n + SG_TPB * 128 - 1) / (SG_TPB * 128), 32));
+    ScopedKTimer tm(b, "segment_max_b", 4.0 * (double)b->nb * (double)n, true);
+    k_seg_max<<<dim3((unsigned)chunks, (unsigned)b->nb, 1), SG_TPB, 0, b->stream>>>(x, n, d_max_bits, tm.stamp());
     VH_CHECK_LAUNCH();
 }
+void vh_seg_max_launch(vh_batch *b, const float *x, uint32_t *d_max_bits) { vh_seg_max_launch_n(b, x, b->V, d_max_bits); }
 
 void vh_proton_stats_launch(vh_batch *b, const float *proton, uint32_t *d_pmax_bits, uint32_t *d_hist) {
     static_assert(SG_TPB == 256, "one thread per histogram bin");

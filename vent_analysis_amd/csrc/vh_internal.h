@@ -339,6 +339,13 @@ struct vh_batch {
     Buf<float> d_proton_src;         // [nb][rs_shape] the proton on its own grid, while state.has_proton_src()
     int64_t rs_shape[3] = {0, 0, 0}; // its shape (Rs, Cs, Zs)
     Buf<int32_t> d_rs_tab;           // [nb][10 (R + C + Z)] the last resampling's tap tables (RsTabs)
+    // vh_batch_register_maps (register_maps.hip): on first demand, and nothing another call reads
+    Buf<uint32_t> d_rm_max;          // [2][nb] bit patterns of the source's and the HPvent's maxima over F
+    Buf<uint8_t> d_rm_cx;            // [nb][V] the 32-level codes of the HPvent, 255 invalid
+    Buf<int32_t> d_rm_tab;           // [nb][10 (Kr R + Kc C + Kz Z)] the last call's tap tables
+    Buf<uint32_t> d_rm_hist;         // [nb][rm_nc][32][32] its joint histograms
+    Buf<double> d_rm_score;          // [nb][rm_nc] its scores
+    int64_t rm_nc = 0;               // its candidates; 0 before any register_maps call
     int64_t n4_subbatch = 0;         // volumes per N4 sub-batch (0 = whole batch)
     int32_t n4_mode = 0;             // vh_run_opts.n4_mode
     bool n4_used_study = false;      // the last N4 ran the volume-resident kernel
@@ -617,6 +624,17 @@ void vh_seg_max_launch(vh_batch *b, const float *x, uint32_t *d_max_bits);
 // joint histogram of every shift of the search window (d_hist [nb][ns][32][32], zeroed here) and the
 // scores (d_score [nb][ns]) of proton against hp; vh_register_takes: the grid fits.
 // vh_shift_launch_*: dst(v) = src(v + shift[study]) inside the volume, 0 elsewhere, d_shift [nb][3]
+#define RG_INVALID 255u
+#define RG_BINS 1024                // 32 x 32
+// in F: finite and >= 0 (NaN fails both comparisons; -0.0 is in F and counts as +0.0), as segment.hip
+__device__ __forceinline__ bool rg_in_f(float x) { return x >= 0.0f && x <= 3.402823466e+38f; }
+// min(255, (int)(x * scale)) >> 3, the product rounded to float32 (one that is not below 255 -- NaN from
+// an infinite scale times zero included -- is bin 255, as in k_seg_hist); 255 outside F
+__device__ __forceinline__ uint32_t rg_code(float x, float scale) {
+    if (!rg_in_f(x)) return RG_INVALID;
+    const float p = __fmul_rn(x, scale);
+    return (uint32_t)(p < 255.0f ? (int)p : 255) >> 3;
+}
 bool vh_register_takes(const vh_batch *b);
 void vh_register_launch(vh_batch *b, const float *proton, const float *hp, const int32_t search[3],
                         uint32_t *d_maxb, uint8_t *d_cp, uint8_t *d_cx, uint32_t *d_hist, double *d_score);
@@ -638,6 +656,29 @@ struct RsPlan {
 };
 bool vh_resample_plan(const vh_batch *b, const int64_t src_shape[3], const int32_t *h_tab, RsPlan &p);
 void vh_resample_launch(vh_batch *b, const RsPlan &p, const float *src, float *dst, const int32_t *d_tab);
+// segment.hip's maximum sweep over n voxels per study instead of the batch's V (a source on its own grid)
+void vh_seg_max_launch_n(vh_batch *b, const float *x, int64_t n, uint32_t *d_max_bits);
+// register_maps.hip: the tap tables of one study's candidate lists as the kernel reads them,
+// 10 (Kr R + Kc C + Kz Z) words: the Kr tables of the r list (each first int32 [R], count int32 [R], weight
+// float [R][8], as RsTabs), then the Kc of the c list, then the Kz of the z list.  vh_register_maps_plan
+// picks the tile, the band and the chunk of the r list from the tables of the whole batch (host copy) and
+// says whether the grid fits; vh_register_maps_launch: the maxima (d_maxb [2][nb]: source, HPvent), the
+// xenon codes (d_cx [nb][V]), the joint histogram of every candidate (d_hist [nb][nc][32][32], zeroed
+// here) and the scores (d_score [nb][nc]) of src [nb][Rs][Cs][Zs] against hp
+struct RmPlan {
+    int Rs, Cs, Zs;      // the source shape
+    int R, C, Z;         // the batch's
+    int Kr, Kc, Kz;      // the candidates of each list
+    int TC, TZ;          // destination columns and slices of a workgroup's tile
+    int BR;              // destination rows of its band
+    int span;            // source rows staged for a band and a chunk: the largest over studies, bands, chunks
+    int ntc, ntz, nbands;
+    int chunk, nchunks;  // r candidates a workgroup serves; chunks of the r list
+};
+bool vh_register_maps_plan(const vh_batch *b, const int64_t src_shape[3], const int32_t count[3],
+                           const int32_t *h_tab, RmPlan &p);
+void vh_register_maps_launch(vh_batch *b, const RmPlan &p, const float *src, const float *hp, const int32_t *d_tab,
+                             uint32_t *d_maxb, uint8_t *d_cx, uint32_t *d_hist, double *d_score);
 void vh_recon_run(hipStream_t st, const double2 *d_in, double2 *d_tmp, double2 *d_out, double2 *d_tw0,
                   double2 *d_tw1, int64_t n0, int64_t n1, int64_t nz);
 void vh_montage_run(hipStream_t s, int64_t R, int64_t C, int64_t Z, const void *proton, int p64,
